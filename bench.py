@@ -1,6 +1,13 @@
 """Decode benchmark: Llama-2-7B int4-g128, single-stream greedy decode at context 2048 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run does only what the headline figure needs: load, one prefill, capture, W warm-up and K timed decode
+steps, the optional output dump, the JSON line. ``--full`` adds every other measurement listed under "Extra
+objects" below (each takes launches or processes of its own). ``--dump-outputs DIR`` writes what the last timed
+step handed back as ``DIR/<name>.npy``: ``token`` (the newest token id, float64), ``logits`` (that step's lm_head
+logits, float32; the fused 4-bit greedy head only) and ``chunk_tokens`` (the ids of the last graph launch's CHUNK
+steps, float64; when the timed region ends on such a launch). Weights and prompt are seeded, so two builds run
+with the same arguments can be compared array for array.
 N > 1 is launched by the driver as ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...``
 and runs tensor parallelism (generate/tp.py sharding, RCCL all-reduce): one stream, so ``value`` is that stream's
 tokens/s (whole job) and scaling is "strong".
@@ -10,7 +17,8 @@ A "step" = one decode token: one replay of the captured HIP graph (32 blocks + l
 are resident in HBM before the timed region. Timed region: barrier + synchronize, K replays, synchronize +
 barrier; the max over ranks is reported.
 
-Extra objects in the JSON line:
+Extra objects in the JSON line (``--full`` only, except step_roofline and the cold prefill figures, which are
+arithmetic on the plain run's own timings):
   roofline      the dominant kernel = the one with the most device time per decode step, chosen in the run
                 between the decode attention (RoPE + KV append + split attention, K/V bytes at the timed
                 position) and the fused RMSNorm + fc_1/fc_2 int4 GEMV + SwiGLU (46.5 MB per launch); each is
@@ -240,7 +248,7 @@ def measure_traffic(att_pos: int, timeout_s: float = 240.0):
 
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not Path(exe).exists():
-        return None, "rocprofv3 not found"
+        return {k: (None, "rocprofv3 not found") for k in ("gemv", "attention")}
     out = Path(tempfile.mkdtemp(prefix="lga_pmc_"))
     cmd = [exe, "--pmc", "FETCH_SIZE", "--output-format", "csv", "-d", str(out), "-o", "pmc", "--",
            sys.executable, str(Path(__file__).resolve()), "--pmc-child", "--pmc-pos", str(att_pos)]
@@ -368,6 +376,32 @@ def time_sampled_decode(model, first, T: int, warmup: int, steps: int, barrier, 
                     "uniform, embedding row gather); sampler_us = that launch alone on one step's logits"}
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """Write ``arrays`` (name -> tensor or ndarray) as ``out_dir/<name>.npy``: floating point as float32 (float64
+    stays float64), integers as float64 (exact for token ids). The files together stay within ``limit`` bytes: an
+    array over its equal share is cut to a fixed sample of its flattened elements (seed 0, ascending indices).
+    Returns name -> written shape."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    written = {}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+            a = (a.float() if a.is_floating_point() and a.dtype != torch.float64 else a).numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
+        written[name] = list(a.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -379,6 +413,12 @@ def main():
                     help="4-bit mode, or 'bf16' for unquantized weights (BASELINE config 2)")
     ap.add_argument("--model", default=MODEL, help="lit_gpt Config name (default: the headline Llama-2-7B)")
     ap.add_argument("--prompt_len", type=int, default=PROMPT_LEN)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: per-kernel rooflines, the rocprofv3 PMC "
+                         "traffic pass, the warm prefill, sampled decode, the CPU baseline (the --no-* options "
+                         "below drop single ones of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (token, logits, ...) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-graph", action="store_true")
@@ -394,7 +434,8 @@ def main():
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
     headline = args.model == MODEL and args.quantize == "int4-g128"
     dense = args.quantize in ("bf16", "none")
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_traffic and not under_profiler and headline:
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_traffic and not under_profiler
+            and headline):
         # before this process initialises the GPU; the attention at the position time_attention() uses below
         traffic = measure_traffic(args.prompt_len + args.warmup + args.steps)
 
@@ -437,11 +478,13 @@ def main():
         prefill_s = time.perf_counter() - t0
         # warm prefill for the MFMA rate (rewrites cache rows 0..T-1 with the same values; the cold first call
         # above also pays code-object loading and is what reference-style tok/s counts)
-        barrier()
-        t0 = time.perf_counter()
-        model(prompt.view(1, -1), torch.arange(T, device=dev), last_token_only=True)
-        torch.cuda.synchronize()
-        prefill_warm_s = time.perf_counter() - t0
+        prefill_warm_s = None
+        if args.full:
+            barrier()
+            t0 = time.perf_counter()
+            model(prompt.view(1, -1), torch.arange(T, device=dev), last_token_only=True)
+            torch.cuda.synchronize()
+            prefill_warm_s = time.perf_counter() - t0
         use_graph = not args.no_graph
         graph_note = None
         if use_graph:
@@ -493,21 +536,31 @@ def main():
             elapsed = float(t.item())
         tok_s = args.steps / elapsed
         ms_step = elapsed / args.steps * 1e3
-        avg_ms, kbytes = time_dominant_kernel(model)
-        att_ms, att_bytes = time_attention(model, T + args.warmup + args.steps)
-        sampled = None
-        from generate.base import graph_sampling
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            # what the last timed step handed back, before any --full measurement touches the model again
+            outs = {"token": dg.token if use_graph else tok}
+            if use_graph and getattr(dg, "logits", None) is not None:
+                outs["logits"] = dg.logits
+            if use_graph and CHUNK > 1 and args.steps >= CHUNK and args.steps % CHUNK == 0:
+                outs["chunk_tokens"] = dg.history
+            dumped = dump_outputs(args.dump_outputs, outs)
+        avg_ms = kbytes = att_ms = att_bytes = sampled = None
+        if args.full:
+            avg_ms, kbytes = time_dominant_kernel(model)
+            att_ms, att_bytes = time_attention(model, T + args.warmup + args.steps)
+            from generate.base import graph_sampling
 
-        if use_graph and not args.no_sample and graph_sampling(model, 0.8, 200):
-            sampled = time_sampled_decode(model, first, T, args.warmup, args.steps, barrier, world)
+            if use_graph and not args.no_sample and graph_sampling(model, 0.8, 200):
+                sampled = time_sampled_decode(model, first, T, args.warmup, args.steps, barrier, world)
 
     cfg_full = Config.from_name(args.model)
     pf_flops = prefill_flops(cfg_full, T, tp=world)
     mean_pos = T + args.warmup + 1 + (args.steps - 1) / 2
     step_bytes = algorithmic_bytes_per_token(cfg_full, mean_pos, tp=world, dense=dense)
     step_gbs = step_bytes * tok_s / 1e9
-    kern_gbs = kbytes / (avg_ms * 1e-3) / 1e9
-    gemv_line = {"bound": "hbm", "kernel": (
+    kern_gbs = kbytes / (avg_ms * 1e-3) / 1e9 if args.full else None
+    gemv_line = None if not args.full else {"bound": "hbm", "kernel": (
                  "gemv_bf16_kernel<.., DUAL> (RMSNorm + fc_1/fc_2 bf16 GEMV + SwiGLU of one block)" if dense else
                  DOMINANT if not cfg._mlp_class == "LLaMAMoE" else
                  "gemv_q4_kernel<.., DUAL> routed (RMSNorm + fc_1/fc_2 of 2 experts + SwiGLU of one block)"),
@@ -555,7 +608,7 @@ def main():
                                                         f" (fused GEMV form off: {gtp.comm.get_default().fused_fallback})"))
                        if gtp.comm.get_default() is not None else
                        f"rccl ({gtp.comm.fallback_reason or 'LGA_TP_ALLREDUCE=rccl'})"} if world > 1 else {})},
-        "roofline": lines[0],
+        "roofline": lines[0] if lines else None,  # the per-kernel lines take launches of their own: --full
         "roofline_secondary": lines[1] if len(lines) > 1 else None,
         "step_roofline": {"bytes_per_token": int(step_bytes), "achieved": round(step_gbs, 1),
                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(step_gbs / HBM_PEAK_GBS, 4),
@@ -566,9 +619,10 @@ def main():
                              "achieved": round(pf_flops / prefill_s / 1e12, 1),
                              "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                              "frac": round(pf_flops / prefill_s / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-                             "warm_seconds": round(prefill_warm_s, 5),
-                             "warm_achieved": round(pf_flops / prefill_warm_s / 1e12, 1),
-                             "warm_frac": round(pf_flops / prefill_warm_s / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+                             **({} if prefill_warm_s is None else {
+                                 "warm_seconds": round(prefill_warm_s, 5),
+                                 "warm_achieved": round(pf_flops / prefill_warm_s / 1e12, 1),
+                                 "warm_frac": round(pf_flops / prefill_warm_s / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)}),
                              "note": "seconds / frac: the FIRST (cold) prefill of the process, wall clock, the one "
                                      "reference-style tok/s counts; warm_*: the same prompt run a second time; every "
                                      "Linear's int4 weights dequantized inside the GEMM, flash attention, norms"},
@@ -580,8 +634,10 @@ def main():
             args.steps + args.warmup + 1) / args.steps), 2),
         "load_s": round(load_s, 2),
         "sampled_decode": sampled,
+        "full": args.full,
+        **({"dumped_outputs": dumped} if dumped is not None else {}),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
         # the reference's CPU path on all the host cores this process may run on — the affinity set,
         # capped by the CPU share the host grants the job (OMP_NUM_THREADS: 16 per GPU on the MI355X pool, whose
         # affinity mask shows the whole machine)
