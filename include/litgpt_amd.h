@@ -30,6 +30,7 @@ typedef struct ihipStream_t* lga_stream_t; /* == hipStream_t */
 #define LGA_FMT_NF4 1 /* bitsandbytes NF4 codebook, per-block fp32 absmax */
 #define LGA_FMT_BF16 2 /* unquantized bf16 weight [N][K] (lga_q4_gemm_fused / lga_q4_gemm_swiglu only) */
 #define LGA_FMT_FP4 3 /* bitsandbytes FP4 code (get_4bit_type('fp4'), "bnb.fp4"), per-block fp32 absmax */
+#define LGA_FMT_INT8 4 /* LLM.int8: int8 [N][K], fp32 row absmax (the lga_int8_* entry points only) */
 
 /* -- plumbing ---------------------------------------------------------------------------------------- */
 const char* lga_last_error_string(void);
@@ -102,6 +103,34 @@ int lga_bf16_gemv_swiglu(const void* x, const void* weight1, const void* weight2
 /* prefill GEMM Y (M, N) = X (M, K) . W (N, K)^T [+bias] [+residual] on MFMA; K % 32 == 0 */
 int lga_bf16_gemm(const void* x, const void* weight, const void* bias, const void* residual, void* y, int M, int N,
                   int K, lga_stream_t stream);
+
+/* -- bnb.int8 (LLM.int8, modelled on bitsandbytes Linear8bitLt(has_fp16_weights=False, threshold=6.0) with bf16 in
+ *    place of fp16; the reference's --quantize bnb.int8, generate/base.py:105) ------------------------------------
+ * Weights: row scale s_w[n] = max_k |W[n,k]| (fp32), q = clamp(rint(W * (127 / s_w)), -127, 127), int8 [N][K].
+ * Activations (per call): column j is an outlier column iff |X[m,j]| >= threshold for any row m (threshold <= 0: no
+ * column is); s_x[m] = max over the other columns, a = clamp(rint(X * (127 / s_x[m])), -127, 127), 0 in outlier
+ * columns. y = bf16(float(sum_j a q) * ((s_x s_w) / 16129) + sum_{j outlier} X[m,j] * (q[n,j] * (s_w / 127)) + bias)
+ * [then bf16(y + residual)]; the integer sum is exact int32. K % 16 == 0 everywhere. */
+/* weight quantizer: weight [N][K] fp32 or bf16 -> qweight int8 [N][K], scales fp32 [N] */
+int lga_int8_quantize(const void* weight, int weight_is_bf16, void* qweight, float* scales, int N, int K,
+                      lga_stream_t stream);
+/* decode GEMV y (N) = x (K) against the int8 weight; optional fused RMSNorm of x, bias, residual; K <= 16384 */
+int lga_int8_gemv(const void* x, const void* qweight, const float* scales, const void* bias, const void* residual,
+                  const void* norm_weight, float norm_eps, float threshold, void* y, int N, int K,
+                  lga_stream_t stream);
+/* y = bf16(silu(bf16(x W1^T))) * bf16(x W2^T), both matrices on one activation quantization */
+int lga_int8_gemv_swiglu(const void* x, const void* qweight1, const float* scales1, const void* qweight2,
+                         const float* scales2, const void* norm_weight, float norm_eps, float threshold, void* y,
+                         int N, int K, lga_stream_t stream);
+/* prefill activation quantizer: x [M][K] bf16 -> xq int8 [M][K], sx fp32 [M], col_flags int32 [K] (1 = outlier
+ * column), cols int32 [K] (the outlier columns, ascending, first *count entries), count int32 [1]; no host sync */
+int lga_int8_quantize_act(const void* x, void* xq, float* sx, int* col_flags, int* cols, int* count, int M, int K,
+                          float threshold, lga_stream_t stream);
+/* prefill GEMM on the i8 MFMA: Y (M, N) from xq / sx / cols / count of lga_int8_quantize_act (x: the bf16 rows, read
+ * in the outlier columns only); M >= 2 */
+int lga_int8_gemm(const void* x, const void* xq, const float* sx, const int* cols, const int* count,
+                  const void* qweight, const float* scales, const void* bias, const void* residual, void* y, int M,
+                  int N, int K, lga_stream_t stream);
 
 /* -- row / elementwise ops ---------------------------------------------------------------------------- */
 /* RMSNorm over rows of n (lit_gpt/rmsnorm.py:19-25) */

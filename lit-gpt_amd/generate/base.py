@@ -9,7 +9,8 @@ short) and ``main`` (:96-187) with the same flags and the same stderr timing lin
     top-k + softmax + inverse-CDF sampler on the device — the role ``--compile`` (CUDA graphs) plays in the
     reference; the sampler's uniforms come from a counter-based RNG seeded from torch's generator, so a seed
     reproduces a run but not the reference's exact torch.multinomial draws;
-  * ``--quantize`` takes this build's formats (int4-g128, nf4 / bnb.nf4 / bnb.nf4-dq, bnb.fp4 / bnb.fp4-dq); without it the Linears
+  * ``--quantize`` takes this build's formats (int4-g128, nf4 / bnb.nf4 / bnb.nf4-dq, bnb.fp4 / bnb.fp4-dq, bnb.int8);
+    without it the Linears
     stay bf16 ``nn.Linear`` (BASELINE config 2) and run on the bf16 GEMV / GEMM kernels;
   * ``--synthetic NAME`` builds a random-init model of a registered config (no checkpoint, no tokenizer): the
     prompt is ``--prompt_len`` synthetic token ids.
@@ -188,6 +189,13 @@ def build_model(config: Config, *, quantize: Optional[str], device: torch.device
         from lit_gpt.quantize import parse_mode
 
         parse_mode(quantize)  # unsupported modes fail before any weight is materialised
+        if quantize == "bnb.int8":  # out of scope for the int8 kernels; refused before any weight is materialised
+            if config._mlp_class == "LLaMAMoE":
+                raise NotImplementedError("--quantize bnb.int8 with a sparse-MoE model: the routed expert kernels "
+                                          "take 4-bit experts only (int4-g128, nf4, bnb.fp4 and their -dq forms)")
+            if fabric is not None and fabric.world_size > 1:
+                raise NotImplementedError("--quantize bnb.int8 with tensor parallelism: the fused GEMV + all-reduce "
+                                          "takes 4-bit or bf16 shards only; run bnb.int8 on one device")
     tp = None
     if fabric is not None and fabric.world_size > 1:
         from generate import tp

@@ -103,7 +103,7 @@ def _lin(linear: nn.Module, x: torch.Tensor, *, reduce=None, **kw) -> torch.Tens
     """Run a Linear on the MI355X kernels. ``reduce``: the TP all-reduce hook of a row-parallel projection
     (generate/tp.py) — the partial output is summed over the ranks (+ ``residual``), fused into the GEMV launch for
     one-token inputs (lit_gpt/comm.py linear_reduce)."""
-    from lit_gpt.quantize import QuantLinear
+    from lit_gpt.quantize import Int8Linear, QuantLinear
 
     if reduce is not None:
         from lit_gpt import comm
@@ -111,7 +111,7 @@ def _lin(linear: nn.Module, x: torch.Tensor, *, reduce=None, **kw) -> torch.Tens
         res = kw.pop("residual", None)
         return comm.linear_reduce(reduce, linear, x, res, lambda: _lin(linear, x, **kw))
 
-    if isinstance(linear, QuantLinear):
+    if isinstance(linear, (QuantLinear, Int8Linear)):
         return linear(x, **kw)
     if isinstance(linear, nn.Linear) and linear.weight.is_cuda and linear.weight.dtype == torch.float32:
         return _dense_f32(linear, x, **kw)
@@ -119,7 +119,8 @@ def _lin(linear: nn.Module, x: torch.Tensor, *, reduce=None, **kw) -> torch.Tens
         return _dense(linear, x, **kw)
     raise NotImplementedError(
         "Linear without MI355X weights: move the model to the GPU in bf16, or convert it with "
-        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4').convert_module(model) (the --quantize flag)")
+        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8').convert_module(model) (the --quantize "
+        "flag)")
 
 
 class GPT(nn.Module):
@@ -406,7 +407,7 @@ class LLaMAMLP(nn.Module):
                 residual: Optional[torch.Tensor] = None, reduce=None) -> torch.Tensor:
         """proj(silu(fc_1 x) * fc_2 x) (model.py:712-716); ``norm``/``residual``/``reduce`` are Block fusion hooks
         (``reduce``: the TP all-reduce of the row-parallel proj, see CausalSelfAttention.forward)."""
-        from lit_gpt.quantize import QuantLinear
+        from lit_gpt.quantize import Int8Linear, QuantLinear
 
         lead, C = x.shape[:-1], x.shape[-1]
         x2 = x.reshape(-1, C).contiguous()
@@ -416,7 +417,13 @@ class LLaMAMLP(nn.Module):
                    and f2.bias is None and (f1.fmt, f1.group) == (f2.fmt, f2.group))
         dense = (M == 1 and type(f1) is nn.Linear and type(f2) is nn.Linear and f1.bias is None and f2.bias is None
                  and f1.weight.is_cuda and f1.weight.shape == f2.weight.shape)
-        if dense:  # bf16 weights: fc_1 || fc_2 + SwiGLU in one GEMV launch, norm_2 fused
+        int8 = (M == 1 and isinstance(f1, Int8Linear) and isinstance(f2, Int8Linear) and f1.bias is None
+                and f2.bias is None and f1.qweight.shape == f2.qweight.shape and f1.threshold == f2.threshold)
+        if int8:  # bnb.int8: fc_1 || fc_2 + SwiGLU in one GEMV launch on one activation quantization, norm_2 fused
+            g = ops.int8_gemv_swiglu(x2.view(-1), f1.qweight, f1.scales, f2.qweight, f2.scales,
+                                     norm_weight=None if norm is None else norm.weight,
+                                     eps=1e-5 if norm is None else norm.eps, threshold=f1.threshold).view(1, -1)
+        elif dense:  # bf16 weights: fc_1 || fc_2 + SwiGLU in one GEMV launch, norm_2 fused
             g = ops.bf16_gemv_swiglu(x2.view(-1), _dense_weight(f1), _dense_weight(f2),
                                      norm_weight=None if norm is None else norm.weight,
                                      eps=1e-5 if norm is None else norm.eps).view(1, -1)

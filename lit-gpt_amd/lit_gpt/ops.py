@@ -26,6 +26,7 @@ FMT_Q4G = 0  # int4, symmetric, per-group bf16 scale
 FMT_NF4 = 1  # bitsandbytes NF4 codebook, per-block fp32 absmax
 FMT_BF16 = 2  # (prefill GEMM only) unquantized bf16 weight
 FMT_FP4 = 3  # bitsandbytes FP4 code, per-block fp32 absmax
+FMT_INT8 = 4  # LLM.int8: int8 (N, K) + fp32 row absmax (the int8_* ops only)
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -52,6 +53,11 @@ SIGNATURES = {
     "lga_bf16_gemv": [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
     "lga_bf16_gemv_swiglu": [_P, _P, _P, _P, _F, _P, _I, _I, _P],
     "lga_bf16_gemm": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "lga_int8_quantize": [_P, _I, _P, _P, _I, _I, _P],
+    "lga_int8_gemv": [_P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P],
+    "lga_int8_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P],
+    "lga_int8_quantize_act": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
+    "lga_int8_gemm": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_rmsnorm": [_P, _P, _P, _I, _I, _F, _P],
     "lga_rope_kv_append": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lga_embedding": [_P, _I, _P, _P, _I, _I, _I, _P],
@@ -307,6 +313,86 @@ def bf16_gemm(x, weight, *, bias=None, residual=None, out=None):
     _check(load_library().lga_bf16_gemm(_dev(x, "x", torch.bfloat16), _dev(weight, "weight", torch.bfloat16),
                                         _opt(bias, "bias", torch.bfloat16), _opt(residual, "residual", torch.bfloat16),
                                         _dev(y, "y", torch.bfloat16), M, N, K, _stream()))
+    return y
+
+
+# ------------------------------------------------------------------------------------------------ bnb.int8
+INT8_THRESHOLD = 6.0  # bitsandbytes Linear8bitLt(threshold=6.0): |x| >= threshold marks an outlier column
+
+
+def int8_quantize(weight: torch.Tensor):
+    """(N, K) fp32/bf16 device weight -> (int8 (N, K), fp32 row absmax (N,)): q = rint(W * (127 / absmax))."""
+    N, K = weight.shape
+    w = weight.contiguous()
+    if w.dtype not in (torch.float32, torch.bfloat16):
+        w = w.float()
+    qw = torch.empty(N, K, dtype=torch.int8, device=w.device)
+    sc = torch.empty(N, dtype=torch.float32, device=w.device)
+    _check(load_library().lga_int8_quantize(_dev(w, "weight"), int(w.dtype == torch.bfloat16), qw.data_ptr(),
+                                            sc.data_ptr(), N, K, _stream()))
+    return qw, sc
+
+
+def int8_gemv(x, qweight, scales, *, bias=None, residual=None, norm_weight=None, eps=1e-5,
+              threshold=INT8_THRESHOLD, out=None):
+    """y (N,) = x (K,) against the LLM.int8 weight: x quantized per call, outlier elements (|x| >= threshold) kept in
+    bf16 [+bias] [+residual]; optional fused RMSNorm of x."""
+    N, K = qweight.shape
+    y = out if out is not None else torch.empty(N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_int8_gemv(_dev(x, "x", torch.bfloat16), _dev(qweight, "qweight", torch.int8),
+                                        _dev(scales, "scales", torch.float32), _opt(bias, "bias", torch.bfloat16),
+                                        _opt(residual, "residual", torch.bfloat16),
+                                        _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps), float(threshold),
+                                        _dev(y, "y", torch.bfloat16), N, K, _stream()))
+    return y
+
+
+def int8_gemv_swiglu(x, qw1, sc1, qw2, sc2, *, norm_weight=None, eps=1e-5, threshold=INT8_THRESHOLD, out=None):
+    """y (N,) = bf16(silu(bf16(x W1^T))) * bf16(x W2^T) with LLM.int8 weights (one activation quantization for
+    both), optional fused RMSNorm of x."""
+    N, K = qw1.shape
+    if tuple(qw2.shape) != (N, K):
+        raise ValueError(f"int8_gemv_swiglu: weight shapes differ {tuple(qw1.shape)} vs {tuple(qw2.shape)}")
+    y = out if out is not None else torch.empty(N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_int8_gemv_swiglu(_dev(x, "x", torch.bfloat16), _dev(qw1, "qw1", torch.int8),
+                                               _dev(sc1, "sc1", torch.float32), _dev(qw2, "qw2", torch.int8),
+                                               _dev(sc2, "sc2", torch.float32),
+                                               _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                               float(threshold), _dev(y, "y", torch.bfloat16), N, K, _stream()))
+    return y
+
+
+def int8_quantize_act(x, *, threshold=INT8_THRESHOLD):
+    """X (M, K) bf16 -> (xq int8 (M, K), sx fp32 (M,), cols int32 (K,), count int32 (1,), col_flags int32 (K,)):
+    a column with any |x| >= threshold is an outlier column (flag 1, listed ascending in cols[:count], 0 in xq);
+    sx is each row's absmax over the other columns. Everything stays on the device."""
+    M, K = x.shape
+    dev = x.device
+    xq = torch.empty(M, K, dtype=torch.int8, device=dev)
+    sx = torch.empty(M, dtype=torch.float32, device=dev)
+    flags = torch.empty(K, dtype=torch.int32, device=dev)
+    cols = torch.empty(K, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    _check(load_library().lga_int8_quantize_act(_dev(x, "x", torch.bfloat16), xq.data_ptr(), sx.data_ptr(),
+                                                flags.data_ptr(), cols.data_ptr(), count.data_ptr(), M, K,
+                                                float(threshold), _stream()))
+    return xq, sx, cols, count, flags
+
+
+def int8_gemm(x, xq, sx, cols, count, qweight, scales, *, bias=None, residual=None, out=None):
+    """Y (M, N) from int8_quantize_act's image of X against the LLM.int8 weight on the i8 MFMA: dequantized integer
+    product + the outlier columns' bf16 term [+bias] [+residual]; M >= 2."""
+    M, K = xq.shape
+    N = qweight.shape[0]
+    if tuple(qweight.shape) != (N, K) or tuple(x.shape) != (M, K):
+        raise ValueError(f"int8_gemm: shapes x {tuple(x.shape)} xq {tuple(xq.shape)} qweight {tuple(qweight.shape)}")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_int8_gemm(_dev(x, "x", torch.bfloat16), _dev(xq, "xq", torch.int8),
+                                        _dev(sx, "sx", torch.float32), _dev(cols, "cols", torch.int32),
+                                        _dev(count, "count", torch.int32), _dev(qweight, "qweight", torch.int8),
+                                        _dev(scales, "scales", torch.float32), _opt(bias, "bias", torch.bfloat16),
+                                        _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
+                                        M, N, K, _stream()))
     return y
 
 

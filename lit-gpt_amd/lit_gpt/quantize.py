@@ -1,4 +1,5 @@
-"""4-bit weight-only quantized Linear — the drop-in for bitsandbytes' ``Linear4bit``.
+"""Quantized Linears — the drop-ins for bitsandbytes' ``Linear4bit`` (4-bit weight-only) and ``Linear8bitLt``
+(``bnb.int8``, LLM.int8).
 
 Reference boundary ("Operator boundary being replaced"): any object used where ``nn.Linear`` is
 expected — ``forward(x[..., in_features]) -> y[..., out_features]`` with attributes ``weight``, ``bias``,
@@ -17,6 +18,11 @@ Modes:
                                               held expanded as fp32 per 64-block (lga_nf4_double_quant)
   "bnb.fp4" / "bnb.fp4-dq"                    bitsandbytes FP4 code ({0, .0625, 8, 12, 4, 6, 2, 3} / 12, sign
                                               bit), fp32 absmax per 64 (+ the same double quantization)
+  "bnb.int8"                                  LLM.int8 (``Int8Linear``): int8 weights with an fp32 absmax per row;
+                                              activations quantized per call to int8 with an absmax per row,
+                                              columns holding any |x| >= 6.0 kept in bf16 (the outlier
+                                              decomposition of Linear8bitLt(has_fp16_weights=False,
+                                              threshold=6.0), bf16 where bitsandbytes computes in fp16)
 Group sizes must divide in_features; for a TP row-shard whose width is not a multiple of the requested group
 (e.g. Llama-2-7B mlp.proj at TP=8: 1376) the largest of {128, 64, 32} that divides it is used.
 """
@@ -59,14 +65,14 @@ _MODES = {
     "bnb.nf4-dq": (ops.FMT_NF4, 64),
     "bnb.fp4": (ops.FMT_FP4, 64),
     "bnb.fp4-dq": (ops.FMT_FP4, 64),
+    "bnb.int8": (ops.FMT_INT8, 0),  # Int8Linear: one fp32 scale per row, no group
 }
 
 
 def parse_mode(mode: str):
     if mode not in _MODES:
         raise NotImplementedError(
-            f"quantize mode {mode!r} is not supported on this build (supported: {sorted(_MODES)}); "
-            "bnb.int8 (LLM.int8 outlier decomposition) has no MI355X kernel")
+            f"quantize mode {mode!r} is not supported on this build (supported: {sorted(_MODES)})")
     return _MODES[mode]
 
 
@@ -153,19 +159,81 @@ class QuantLinear(nn.Module):
         return f"in_features={self.in_features}, out_features={self.out_features}, {kind}, group={self.group}"
 
 
+class Int8Linear(nn.Module):
+    """LLM.int8 Linear: ``qweight`` (N, K) int8 + ``scales`` (N,) fp32 row absmax on the GPU (bitsandbytes
+    ``Linear8bitLt(has_fp16_weights=False, threshold=6.0)`` with bf16 in place of fp16).
+
+    ``forward`` follows ``QuantLinear.forward``: one token -> ``lga_int8_gemv`` (RMSNorm / bias / residual fused,
+    activation quantization and outlier columns inside the launch), several -> RMSNorm, ``lga_int8_quantize_act``
+    and the i8 MFMA GEMM ``lga_int8_gemm``. Nothing synchronises with the host."""
+
+    threshold = ops.INT8_THRESHOLD
+
+    def __init__(self, in_features: int, out_features: int, bias: Optional[torch.Tensor] = None, device=None):
+        super().__init__()
+        if in_features % 16:
+            raise ValueError(f"in_features={in_features} is not a multiple of 16; the int8 kernels read 16-B chunks")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("qweight", torch.empty(out_features, in_features, dtype=torch.int8, device=device))
+        self.register_buffer("scales", torch.empty(out_features, dtype=torch.float32, device=device))
+        self.bias = None if bias is None else nn.Parameter(bias.to(torch.bfloat16), requires_grad=False)
+
+    @property
+    def weight(self) -> torch.Tensor:
+        return self.qweight
+
+    @classmethod
+    def from_float(cls, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                   device: Optional[torch.device] = None) -> "Int8Linear":
+        N, K = weight.shape
+        device = device or (weight.device if weight.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        m = cls(K, N, None if bias is None else bias.detach().to(device), device=device)
+        qw, sc = ops.int8_quantize(weight.detach().to(device))
+        m.qweight.copy_(qw)
+        m.scales.copy_(sc)
+        return m
+
+    def forward(self, x: torch.Tensor, *, residual: Optional[torch.Tensor] = None,
+                norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5) -> torch.Tensor:
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, self.in_features)
+        if x2.dtype != torch.bfloat16:
+            raise TypeError(f"Int8Linear expects bf16 activations (bf16-true), got {x2.dtype}")
+        x2 = x2.contiguous()
+        M = x2.shape[0]
+        res = None if residual is None else residual.reshape(M, self.out_features).contiguous()
+        if M == 1:
+            y = ops.int8_gemv(x2.view(-1), self.qweight, self.scales, bias=self.bias,
+                              residual=None if res is None else res.view(-1), norm_weight=norm_weight, eps=norm_eps,
+                              threshold=self.threshold)
+        else:
+            if norm_weight is not None:
+                x2 = ops.rmsnorm(x2, norm_weight, norm_eps)
+            xq, sx, cols, count, _ = ops.int8_quantize_act(x2, threshold=self.threshold)
+            y = ops.int8_gemm(x2, xq, sx, cols, count, self.qweight, self.scales, bias=self.bias, residual=res)
+        return y.view(*lead, self.out_features)
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, int8, "
+                f"threshold={self.threshold}")
+
+
 class QuantizedPrecision:
     """Stand-in for Lightning's ``BitsandbytesPrecision(mode, dtype)`` (generate/base.py:128-134)."""
 
     def __init__(self, mode: str, dtype: torch.dtype = torch.bfloat16) -> None:
         parse_mode(mode)
         if dtype != torch.bfloat16:
-            raise NotImplementedError("the MI355X 4-bit path computes in bf16 (precision bf16-true)")
+            raise NotImplementedError("the MI355X quantized path computes in bf16 (precision bf16-true)")
         self.mode, self.dtype = mode, dtype
 
     def convert_module(self, module: nn.Module, device: Optional[torch.device] = None) -> nn.Module:
-        """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` quantized on ``device``."""
+        """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` (``Int8Linear`` for ``bnb.int8``)
+        quantized on ``device``."""
         for name, child in list(module.named_children()):
-            if isinstance(child, nn.Linear):
+            if isinstance(child, nn.Linear) and self.mode == "bnb.int8":
+                setattr(module, name, Int8Linear.from_float(child.weight, child.bias, device))
+            elif isinstance(child, nn.Linear):
                 setattr(module, name, QuantLinear.from_float(child.weight, child.bias, self.mode, device))
             else:
                 self.convert_module(child, device)
