@@ -23,7 +23,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
-from lit_gpt import ops
+from lit_gpt import ops, quantize
 
 DEFAULT_CAP = 32768  # bf16 elements per message (64 KB): decode activations of every config (k * C for MoE)
 
@@ -323,14 +323,11 @@ def linear_reduce(hook, lin: torch.nn.Module, x: torch.Tensor, residual: Optiona
     """The row-parallel Linear under TP, its all-reduce hook and the Block residual add: ONE fused launch
     (``XgmiAllReduce.gemv_all_reduce``) for a one-token 4-bit Linear when a communicator is installed, else
     ``compute()`` (the plain Linear) followed by the hook's reduction (+ residual)."""
-    from lit_gpt.quantize import QuantLinear
-
     comm = _default
     world = hook.args[0]
-    if (comm is not None and comm.world == world and isinstance(lin, QuantLinear) and x.numel() == lin.in_features
-            and x.dtype == torch.bfloat16 and x.is_cuda and comm.supports_rows(lin.out_features)
-            and (residual is None or residual.numel() == lin.out_features) and fused_gemv_allreduce
-            and getattr(comm, "fused_ok", True)):
+    if (comm is not None and comm.world == world and quantize.gemv_allreduce_supported(lin, x)
+            and comm.supports_rows(lin.out_features) and (residual is None or residual.numel() == lin.out_features)
+            and fused_gemv_allreduce and getattr(comm, "fused_ok", True)):
         y = comm.gemv_all_reduce(lin, x.reshape(-1), residual)
         return y.view(*x.shape[:-1], lin.out_features)
     h = compute()

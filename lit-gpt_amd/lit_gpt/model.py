@@ -28,99 +28,19 @@ from typing import Any, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from lit_gpt import ops
+from lit_gpt import comm, ops, quantize
 from lit_gpt.config import Config
-from lit_gpt.rmsnorm import RMSNorm
-
-
-
-def _gpu_only(what: str) -> None:
-    raise RuntimeError(f"{what}: this build computes on the MI355X only (no CPU path); move the model to 'cuda'")
-
-
-def _dense_weight(linear: nn.Linear) -> torch.Tensor:
-    """The bf16 weight of an unquantized Linear, made contiguous once in place (a TP row shard from
-    ``generate/tp.py``'s ``tensor_split(dim=1)`` is a strided view)."""
-    w = linear.weight
-    if w.dtype != torch.bfloat16:
-        raise TypeError(f"unquantized Linear on the MI355X path expects bf16 weights (bf16-true), got {w.dtype}")
-    if not w.is_contiguous():
-        linear.weight.data = w.data.contiguous()
-        w = linear.weight
-    return w
-
-
-def _dense(linear: nn.Linear, x: torch.Tensor, *, residual: Optional[torch.Tensor] = None,
-           norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5) -> torch.Tensor:
-    """F.linear with bf16 weights (BASELINE config 2): one token -> lga_bf16_gemv (RMSNorm / residual fused),
-    several -> lga_bf16_gemm (MFMA)."""
-    w = _dense_weight(linear)
-    N, K = w.shape
-    lead = x.shape[:-1]
-    x2 = x.reshape(-1, K)
-    if x2.dtype != torch.bfloat16:
-        raise TypeError(f"Linear expects bf16 activations (bf16-true), got {x2.dtype}")
-    x2 = x2.contiguous()
-    M = x2.shape[0]
-    b = None if linear.bias is None else linear.bias.to(torch.bfloat16)
-    res = None if residual is None else residual.reshape(M, N).contiguous()
-    if M == 1:
-        y = ops.bf16_gemv(x2.view(-1), w, bias=b, residual=None if res is None else res.view(-1),
-                          norm_weight=norm_weight, eps=norm_eps)
-    else:
-        if norm_weight is not None:
-            x2 = ops.rmsnorm(x2, norm_weight, norm_eps)
-        if _fused_prefill(M, N, K, 64, 2):  # MFMA tiles with the weight DMA'd as stored (csrc/gemm_q4f.hip)
-            y = ops.q4_gemm_fused(x2, w, None, N, K, 64, 2, bias=b, residual=res)
-        else:
-            y = ops.bf16_gemm(x2, w, bias=b, residual=res)
-    return y.view(*lead, N)
-
-
-def _dense_f32(linear: nn.Linear, x: torch.Tensor, *, residual: Optional[torch.Tensor] = None,
-               norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5) -> torch.Tensor:
-    """F.linear in float32 (the reference's --precision 32-true, BASELINE config 1): lga_f32_linear."""
-    if norm_weight is not None:
-        raise NotImplementedError("fp32 path: RMSNorm-family blocks are not built in fp32 (GPT-NeoX LayerNorm is)")
-    w = linear.weight
-    if not w.is_contiguous():
-        linear.weight.data = w.data.contiguous()
-        w = linear.weight
-    N, K = w.shape
-    if x.dtype != torch.float32:
-        raise TypeError(f"fp32 Linear expects fp32 activations (32-true), got {x.dtype}")
-    lead = x.shape[:-1]
-    x2 = x.reshape(-1, K).contiguous()
-    res = None if residual is None else residual.reshape(x2.shape[0], N).contiguous()
-    return ops.f32_linear(x2, w, bias=linear.bias, residual=res).view(*lead, N)
-
-
-def _fused_prefill(M: int, N: int, K: int, group: int, fmt: int) -> bool:
-    return M > 1 and ops.q4f_fits(M, N, K, group, fmt)
+from lit_gpt.rmsnorm import RMSNorm, _gpu_only
 
 
 def _lin(linear: nn.Module, x: torch.Tensor, *, reduce=None, **kw) -> torch.Tensor:
-    """Run a Linear on the MI355X kernels. ``reduce``: the TP all-reduce hook of a row-parallel projection
-    (generate/tp.py) — the partial output is summed over the ranks (+ ``residual``), fused into the GEMV launch for
-    one-token inputs (lit_gpt/comm.py linear_reduce)."""
-    from lit_gpt.quantize import Int8Linear, QuantLinear
-
+    """Run a Linear on the MI355X kernels (lit_gpt/quantize.py ``kernels``). ``reduce``: the TP all-reduce hook of a
+    row-parallel projection (generate/tp.py) — the partial output is summed over the ranks (+ ``residual``), fused
+    into the GEMV launch for one-token inputs (lit_gpt/comm.py linear_reduce)."""
     if reduce is not None:
-        from lit_gpt import comm
-
         res = kw.pop("residual", None)
-        return comm.linear_reduce(reduce, linear, x, res, lambda: _lin(linear, x, **kw))
-
-    if isinstance(linear, (QuantLinear, Int8Linear)):
-        return linear(x, **kw)
-    if isinstance(linear, nn.Linear) and linear.weight.is_cuda and linear.weight.dtype == torch.float32:
-        return _dense_f32(linear, x, **kw)
-    if isinstance(linear, nn.Linear) and linear.weight.is_cuda:
-        return _dense(linear, x, **kw)
-    raise NotImplementedError(
-        "Linear without MI355X weights: move the model to the GPU in bf16, or convert it with "
-        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8').convert_module(model) (the --quantize "
-        "flag)")
+        return comm.linear_reduce(reduce, linear, x, res, lambda: quantize.kernels(linear)(x, **kw))
+    return quantize.kernels(linear)(x, **kw)
 
 
 class GPT(nn.Module):
@@ -255,8 +175,6 @@ class Block(nn.Module):
         # tensor parallelism (generate/tp.py's all_reduce_output hook on attn / mlp) the projections yield partial
         # sums: the module then runs without its hook and the reduction + residual add is one fused kernel
         # (lit_gpt/comm.py); any other forward hook keeps the reference's call-the-module semantics.
-        from lit_gpt import comm
-
         ha = comm.tp_hook(self.attn)
         hm = comm.tp_hook(self.mlp)
         if ha is not None:
@@ -407,45 +325,8 @@ class LLaMAMLP(nn.Module):
                 residual: Optional[torch.Tensor] = None, reduce=None) -> torch.Tensor:
         """proj(silu(fc_1 x) * fc_2 x) (model.py:712-716); ``norm``/``residual``/``reduce`` are Block fusion hooks
         (``reduce``: the TP all-reduce of the row-parallel proj, see CausalSelfAttention.forward)."""
-        from lit_gpt.quantize import Int8Linear, QuantLinear
-
         lead, C = x.shape[:-1], x.shape[-1]
-        x2 = x.reshape(-1, C).contiguous()
-        M = x2.shape[0]
-        f1, f2 = self.fc_1, self.fc_2
-        fusable = (M == 1 and isinstance(f1, QuantLinear) and isinstance(f2, QuantLinear) and f1.bias is None
-                   and f2.bias is None and (f1.fmt, f1.group) == (f2.fmt, f2.group))
-        dense = (M == 1 and type(f1) is nn.Linear and type(f2) is nn.Linear and f1.bias is None and f2.bias is None
-                 and f1.weight.is_cuda and f1.weight.shape == f2.weight.shape)
-        int8 = (M == 1 and isinstance(f1, Int8Linear) and isinstance(f2, Int8Linear) and f1.bias is None
-                and f2.bias is None and f1.qweight.shape == f2.qweight.shape and f1.threshold == f2.threshold)
-        if int8:  # bnb.int8: fc_1 || fc_2 + SwiGLU in one GEMV launch on one activation quantization, norm_2 fused
-            g = ops.int8_gemv_swiglu(x2.view(-1), f1.qweight, f1.scales, f2.qweight, f2.scales,
-                                     norm_weight=None if norm is None else norm.weight,
-                                     eps=1e-5 if norm is None else norm.eps, threshold=f1.threshold).view(1, -1)
-        elif dense:  # bf16 weights: fc_1 || fc_2 + SwiGLU in one GEMV launch, norm_2 fused
-            g = ops.bf16_gemv_swiglu(x2.view(-1), _dense_weight(f1), _dense_weight(f2),
-                                     norm_weight=None if norm is None else norm.weight,
-                                     eps=1e-5 if norm is None else norm.eps).view(1, -1)
-        elif fusable:
-            if norm is not None and not ops.gemv_fuses_norm(C, dual=True):
-                x2, norm = norm(x2), None
-            g = ops.q4_gemv_swiglu(x2.view(-1), f1.qweight, f1.scales, f2.qweight, f2.scales, f1.out_features, C,
-                                   f1.group, f1.fmt, norm_weight=None if norm is None else norm.weight,
-                                   eps=1e-5 if norm is None else norm.eps).view(1, -1)
-        else:
-            n = x2 if norm is None else norm(x2)
-            g = None
-            if f1.bias is None and f2.bias is None:  # fc_1 || fc_2 + SwiGLU in one fused GEMM launch
-                I = f1.out_features
-                if (isinstance(f1, QuantLinear) and isinstance(f2, QuantLinear)
-                        and (f1.fmt, f1.group) == (f2.fmt, f2.group) and _fused_prefill(M, I, C, f1.group, f1.fmt)):
-                    g = ops.q4_gemm_swiglu(n, f1.qweight, f1.scales, f2.qweight, f2.scales, I, C, f1.group, f1.fmt)
-                elif (type(f1) is nn.Linear and type(f2) is nn.Linear and f1.weight.is_cuda
-                      and f1.weight.shape == f2.weight.shape and _fused_prefill(M, I, C, 64, 2)):
-                    g = ops.q4_gemm_swiglu(n, _dense_weight(f1), None, _dense_weight(f2), None, I, C, 64, 2)
-            if g is None:
-                g = ops.swiglu(_lin(f1, n).contiguous(), _lin(f2, n).contiguous())
+        g = quantize.swiglu(self.fc_1, self.fc_2, x.reshape(-1, C).contiguous(), norm)
         out = _lin(self.proj, g, residual=residual, reduce=reduce)
         return out.view(*lead, -1)
 
@@ -484,15 +365,13 @@ class LLaMAMoE(nn.Module):
         expert's buffers at its slice, so the routed GEMVs and the grouped GEMMs index experts with one stride
         (done once: ``build_model`` calls it right after quantizing the block, so the first prompt does not pay the
         copy — 32 ms of Mixtral-8x7B's cold prefill in round 4)."""
-        from lit_gpt.quantize import QuantLinear
-
         if self._stacks is not None and self._stacks[0][0].data_ptr() == self.experts[0].fc_1.qweight.data_ptr():
             return self._stacks
         out = []
         for name in ("fc_1", "fc_2", "proj"):
             lins = [getattr(e, name) for e in self.experts]
             l0 = lins[0]
-            if not all(isinstance(l, QuantLinear) and l.bias is None and (l.fmt, l.group, l.qweight.shape) ==
+            if not all(isinstance(l, quantize.QuantLinear) and l.bias is None and (l.fmt, l.group, l.qweight.shape) ==
                        (l0.fmt, l0.group, l0.qweight.shape) for l in lins):
                 raise NotImplementedError("LLaMAMoE on the MI355X needs bias-free QuantLinear experts of one format")
             qw = torch.stack([l.qweight for l in lins])
@@ -505,21 +384,15 @@ class LLaMAMoE(nn.Module):
 
     def _grouped_ok(self, C: int) -> bool:
         """The grouped prefill GEMMs take 4-bit experts whose shapes the fused MFMA kernel covers (else the loop)."""
-        from lit_gpt.quantize import QuantLinear
-
-        f1, pj = self.experts[0].fc_1, self.experts[0].proj
-        if not isinstance(f1, QuantLinear) or not isinstance(pj, QuantLinear):
-            return False
+        f1, pj = self.experts[0].fc_1, self.experts[0].proj  # (4-bit: _stack has checked)
         return bool(ops.q4f_fits(64, f1.out_features, C, f1.group, f1.fmt)
                     and ops.q4f_fits(64, pj.out_features, pj.in_features, pj.group, pj.fmt))
 
     def _gate_route_ok(self, C: int) -> bool:
         """One-token routing through ``lga_moe_gate_route``: a bias-free 4-bit gate without forward hooks (the
         reference's TP keeps the gate replicated and hook-free, generate/tp.py:58-62) whose shape the kernel takes."""
-        from lit_gpt.quantize import QuantLinear
-
         g = self.gate
-        return (moe_gate_route and isinstance(g, QuantLinear) and g.bias is None and not g._forward_hooks
+        return (moe_gate_route and isinstance(g, quantize.QuantLinear) and g.bias is None and not g._forward_hooks
                 and g.in_features == C and ops.moe_gate_route_fits(g.out_features, C))
 
     def _expert_hooks(self, x: torch.Tensor, eout: torch.Tensor) -> torch.Tensor:
@@ -543,7 +416,7 @@ class LLaMAMoE(nn.Module):
         f1, pj = self.experts[0].fc_1, self.experts[0].proj
         res = None if residual is None else residual.reshape(T, C).contiguous()
         if T == 1:
-            fuse_norm = norm is not None and ops.gemv_fuses_norm(C, dual=True)
+            fuse_norm = norm is not None and f1.gemv_fuses_norm(dual=True)
             xin = x2 if (norm is None or fuse_norm) else norm(x2)
             nw = norm.weight if fuse_norm else None
             eps = norm.eps if fuse_norm else 1e-5

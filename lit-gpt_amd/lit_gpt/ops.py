@@ -505,14 +505,6 @@ class HeadWorkspace:
         self.buf = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=device)
 
 
-def head_argmax_supported(lin) -> bool:
-    """Whether lga_q4_gemv_argmax_embed covers this lm_head: a 4-bit QuantLinear with K <= 4096, no bias."""
-    from lit_gpt.quantize import QuantLinear
-
-    return (isinstance(lin, QuantLinear) and lin.bias is None and lin.in_features <= 4096
-            and lin.in_features % 32 == 0 and lin.qweight.is_cuda)
-
-
 def q4_gemv_argmax_embed(x, lin, work: HeadWorkspace, *, norm_weight=None, eps=1e-5, table=None, emb_out=None,
                          logits=None, out_idx=None, token_out=None, pos_inout=None):
     """Greedy decode head in one launch: logits = lm_head(RMSNorm(x)), token = argmax(logits) (torch.argmax order),
@@ -847,9 +839,3 @@ def moe_combine(expert_out, probs, ids, residual=None, out=None):
                                           _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
                                           T, k, C, _stream()))
     return y
-
-
-def gemv_fuses_norm(K: int, dual: bool) -> bool:
-    """Whether lga_q4_gemv(_swiglu) can fuse the RMSNorm prologue: the row must fit one K tile
-    (64 lanes x 2 chunks x 32 for the dual SwiGLU GEMV, x 4 chunks otherwise)."""
-    return K // 32 <= (128 if dual else 256)

@@ -17,7 +17,7 @@ from typing import Optional
 
 import torch
 
-from lit_gpt import ops
+from lit_gpt import ops, quantize
 
 class DecodeGraph:
     def __init__(self, model, first_token: torch.Tensor, first_pos: int, chunk: int = 1, *,
@@ -66,7 +66,7 @@ class DecodeGraph:
         fuse = self.fuse_embedding
         model = self.model
         ln = model.transformer.ln_f
-        if (self.temperature == 0.0 and fuse and self.fuse_head and ops.head_argmax_supported(model.lm_head)
+        if (self.temperature == 0.0 and fuse and self.fuse_head and quantize.head_argmax_supported(model.lm_head)
                 and type(ln).__name__ == "RMSNorm" and not model.lm_head._forward_hooks):
             h = model(self.token, self.pos, last_token_only=True, embedded=self.x_emb if embedded else None,
                       hidden_only=True).reshape(-1)
