@@ -132,6 +132,29 @@ int lga_int8_gemm(const void* x, const void* xq, const float* sx, const int* col
                   const void* qweight, const float* scales, const void* bias, const void* residual, void* y, int M,
                   int N, int K, lga_stream_t stream);
 
+/* -- LoRA adapters (the reference's lit_gpt/lora.py: the unmerged LoRALinear / LoRAQKVLinear forward :170-177,
+ *    :398-433 and LoRALinear.merge :140-149, under bf16-true) --------------------------------------------------
+ * Device layout, built once when the adapter is attached: A (R, K) bf16; B (N, r) bf16 in output-row order;
+ * row_off (N) int32 = the first of the r rows of A that output row n uses (a fused qkv Linear: one segment of r rows
+ * per enabled q / k / v slot, -1 on the rows of a slot without adapter), NULL when every row uses rows 0..r-1.
+ * r % 8 == 0 and R % 8 == 0 (zero padded), r <= 64, r <= R <= 192, K % 8 == 0, K <= 32768. Per output row, with
+ * fp32 sums: t_j = bf16(sum_k x'_k A[j,k]); u_n = bf16(sum_{j<r} B[n,j] t[off_n + j]); l_n = bf16(u_n * scaling);
+ * y_n = bf16(base_n + l_n) (base NULL: y_n = l_n); then y_n = bf16(y_n + residual_n) where residual is given.
+ * Rows with off_n < 0 pass base (+ residual) through. base may alias y. */
+/* decode, M = 1, the whole chain in one launch: x' = x, or bf16(RMSNorm(x)) (as lga_q4_gemv) with norm_weight */
+int lga_lora_gemv(const void* x, const void* norm_weight, float norm_eps, const void* A, const void* B,
+                  const int32_t* row_off, float scaling, const void* base, const void* residual, void* y, int N,
+                  int K, int R, int r, lga_stream_t stream);
+/* prefill, M > 1: t (M, R) bf16 = bf16(x A^T) on the MFMA (x already normed), then the rest of the chain per row over
+ * the base output y (M, N) */
+int lga_lora_down(const void* x, const void* A, void* t, int M, int K, int R, lga_stream_t stream);
+int lga_lora_up(const void* t, const void* B, const int32_t* row_off, float scaling, const void* base,
+                const void* residual, void* y, int M, int N, int R, int r, lga_stream_t stream);
+/* in place on a bf16 weight W (N, K): W[n,k] = bf16(W[n,k] + bf16(bf16(sum_j B[n,j] A[off_n + j, k]) * scaling));
+ * rows with off_n < 0 stay untouched */
+int lga_lora_merge(void* W, const void* A, const void* B, const int32_t* row_off, float scaling, int N, int K,
+                   int R, int r, lga_stream_t stream);
+
 /* -- row / elementwise ops ---------------------------------------------------------------------------- */
 /* RMSNorm over rows of n (lit_gpt/rmsnorm.py:19-25) */
 int lga_rmsnorm(const void* x, const void* weight, void* y, int rows, int n, float eps, lga_stream_t stream);

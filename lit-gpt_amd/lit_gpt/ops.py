@@ -58,6 +58,10 @@ SIGNATURES = {
     "lga_int8_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P],
     "lga_int8_quantize_act": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     "lga_int8_gemm": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "lga_lora_gemv": [_P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
+    "lga_lora_down": [_P, _P, _P, _I, _I, _I, _P],
+    "lga_lora_up": [_P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
+    "lga_lora_merge": [_P, _P, _P, _P, _F, _I, _I, _I, _I, _P],
     "lga_rmsnorm": [_P, _P, _P, _I, _I, _F, _P],
     "lga_rope_kv_append": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lga_embedding": [_P, _I, _P, _P, _I, _I, _I, _P],
@@ -394,6 +398,87 @@ def int8_gemm(x, xq, sx, cols, count, qweight, scales, *, bias=None, residual=No
                                         _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
                                         M, N, K, _stream()))
     return y
+
+
+# ------------------------------------------------------------------------------------------------ LoRA
+LORA_MAX_RANK = 64  # r after padding to a multiple of 8
+LORA_MAX_ROWS = 192  # R: rows of A over all segments
+LORA_MAX_K = 32768
+
+
+def _lora_dims(A, B, row_off, name):
+    """(N, K, R, r) of an adapter in the device layout (include/litgpt_amd.h), refusing what the kernels do not
+    take."""
+    (R, K), (N, r) = A.shape, B.shape
+    if r % 8 or R % 8 or not 0 < r <= LORA_MAX_RANK or not r <= R <= LORA_MAX_ROWS or K % 8 or K > LORA_MAX_K:
+        raise ValueError(f"{name}: adapter with r={r}, R={R}, K={K} is outside the kernels' limits (r % 8 == 0, "
+                         f"r <= {LORA_MAX_RANK}, R % 8 == 0, R <= {LORA_MAX_ROWS}, K % 8 == 0, K <= {LORA_MAX_K})")
+    if row_off is not None and row_off.numel() != N:
+        raise ValueError(f"{name}: row_off holds {row_off.numel()} entries, B has {N} rows")
+    if row_off is None and R != r:
+        raise ValueError(f"{name}: A has {R} rows for r={r}: a segmented adapter needs row_off")
+    return N, K, R, r
+
+
+def lora_gemv(x, A, B, row_off, scaling, *, base=None, residual=None, norm_weight=None, eps=1e-5, out=None):
+    """One row: y (N,) = [base +] bf16(bf16(B t) * scaling) [+ residual], t = bf16(A x'), x' = x or its RMSNorm — the
+    whole chain in one launch (``out`` may be ``base``)."""
+    N, K, R, r = _lora_dims(A, B, row_off, "lora_gemv")
+    if x.numel() != K:
+        raise ValueError(f"lora_gemv: x holds {x.numel()} elements, A has {K} columns")
+    for name, v in (("base", base), ("residual", residual), ("out", out)):
+        if v is not None and v.numel() != N:
+            raise ValueError(f"lora_gemv: {name} holds {v.numel()} elements, B has {N} rows")
+    y = out if out is not None else torch.empty(N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_lora_gemv(_dev(x, "x", torch.bfloat16), _opt(norm_weight, "norm_weight", torch.bfloat16),
+                                        float(eps), _dev(A, "A", torch.bfloat16), _dev(B, "B", torch.bfloat16),
+                                        _opt(row_off, "row_off", torch.int32), float(scaling),
+                                        _opt(base, "base", torch.bfloat16), _opt(residual, "residual", torch.bfloat16),
+                                        _dev(y, "y", torch.bfloat16), N, K, R, r, _stream()))
+    return y
+
+
+def lora_down(x, A, out=None):
+    """t (M, R) = bf16(x (M, K) . A (R, K)^T) on the MFMA (prefill)."""
+    M, K = x.shape
+    R = A.shape[0]
+    if A.shape[1] != K or K % 8 or K > LORA_MAX_K or R % 8 or not 0 < R <= LORA_MAX_ROWS:
+        raise ValueError(f"lora_down: x {tuple(x.shape)} against A {tuple(A.shape)} is outside the kernel's limits "
+                         f"(K % 8 == 0, K <= {LORA_MAX_K}, R % 8 == 0, R <= {LORA_MAX_ROWS})")
+    t = out if out is not None else torch.empty(M, R, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_lora_down(_dev(x, "x", torch.bfloat16), _dev(A, "A", torch.bfloat16),
+                                        _dev(t, "t", torch.bfloat16), M, K, R, _stream()))
+    return t
+
+
+def lora_up(t, B, row_off, scaling, *, base=None, residual=None, out=None):
+    """y (M, N) = [base +] bf16(bf16(t B^T per segment) * scaling) [+ residual] (``out`` may be ``base``)."""
+    M, R = t.shape
+    N, r = B.shape
+    if r % 8 or R % 8 or not 0 < r <= LORA_MAX_RANK or not r <= R <= LORA_MAX_ROWS:
+        raise ValueError(f"lora_up: r={r}, R={R} is outside the kernel's limits")
+    if (row_off is None and R != r) or (row_off is not None and row_off.numel() != N):
+        raise ValueError("lora_up: row_off must hold one entry per row of B (and is needed when R != r)")
+    for name, v in (("base", base), ("residual", residual), ("out", out)):
+        if v is not None and v.numel() != M * N:
+            raise ValueError(f"lora_up: {name} holds {v.numel()} elements, expected {M} x {N}")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=t.device)
+    _check(load_library().lga_lora_up(_dev(t, "t", torch.bfloat16), _dev(B, "B", torch.bfloat16),
+                                      _opt(row_off, "row_off", torch.int32), float(scaling),
+                                      _opt(base, "base", torch.bfloat16), _opt(residual, "residual", torch.bfloat16),
+                                      _dev(y, "y", torch.bfloat16), M, N, R, r, _stream()))
+    return y
+
+
+def lora_merge(weight, A, B, row_off, scaling):
+    """In place on the bf16 weight (N, K): W = bf16(W + bf16(bf16(B A per segment) * scaling)); returns it."""
+    N, K, R, r = _lora_dims(A, B, row_off, "lora_merge")
+    if tuple(weight.shape) != (N, K):
+        raise ValueError(f"lora_merge: weight {tuple(weight.shape)} against an adapter for ({N}, {K})")
+    _check(load_library().lga_lora_merge(_dev(weight, "weight", torch.bfloat16), _dev(A, "A", torch.bfloat16),
+                                         _dev(B, "B", torch.bfloat16), _opt(row_off, "row_off", torch.int32),
+                                         float(scaling), N, K, R, r, _stream()))
+    return weight
 
 
 # ------------------------------------------------------------------------------------------------ row ops
