@@ -366,6 +366,28 @@ int lga_f32_attention(const float* q, const float* k_cache, const float* v_cache
 int lga_argmax_f32(const float* logits, int n, int64_t* out_idx, int32_t* token_out, int64_t* pos_inout,
                    lga_stream_t stream);
 
+/* -- log-likelihood scoring (eval/lm_eval_harness.py: log_softmax over the model's full output, gathered at the
+ *    continuation tokens, and the greedy match) — csrc/score.hip --------------------------------------------------
+ * logits: rows x n, contiguous row-major, bf16 (2-B aligned; any n, rows need no further alignment), n <= 2^30.
+ * One pass per row (running max and sum in fp32; the logits are read once), fixed reduction order per row: a row's
+ * result depends on neither `rows` nor the row's position.
+ *   logprob_out[r] = float(x[r, t_r]) - (m_r + log sum_j exp(float(x[r, j]) - m_r)),  m_r = max_j x[r, j]
+ *   argmax_out[r]  = lga_argmax's choice for the row (torch.argmax order: NaN first, ties to the lowest index)
+ * -inf entries contribute 0; a -inf target gives -inf; a row holding NaN or +inf, or all -inf, gives NaN (as
+ * torch.log_softmax); a target outside [0, n) gives NaN and reads nothing. No allocation, no workspace. */
+int lga_token_logprobs(const void* logits, int rows, int n, const int32_t* targets, float* logprob_out,
+                       int32_t* argmax_out, lga_stream_t stream);
+/* the same over fp32 logits (--precision 32-true) */
+int lga_token_logprobs_f32(const float* logits, int rows, int n, const int32_t* targets, float* logprob_out,
+                           int32_t* argmax_out, lga_stream_t stream);
+/* Two models' logits for the same rows (bf16, rows x n each), one pass over both:
+ *   kl_out[r]    = sum_j softmax(p_r)_j (log_softmax(p_r)_j - log_softmax(q_r)_j), evaluated as
+ *                  E_p[p_j - q_j] - (lse(p_r) - lse(q_r)); not clamped (may be slightly negative); entries of zero
+ *                  weight under p contribute 0
+ *   agree_out[r] = 1 when both rows have the same argmax (rule above), else 0 */
+int lga_logits_kl(const void* p_logits, const void* q_logits, int rows, int n, float* kl_out, int32_t* agree_out,
+                  lga_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

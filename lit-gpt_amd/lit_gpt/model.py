@@ -171,6 +171,11 @@ class Block(nn.Module):
         if not isinstance(self.norm_1, RMSNorm) or not isinstance(self.mlp, (LLaMAMLP, LLaMAMoE)):
             raise NotImplementedError(f"{type(self.mlp).__name__} / {type(self.norm_1).__name__} blocks have no "
                                       "MI355X kernels in this build")
+        if input_pos is not None and isinstance(self.mlp, LLaMAMoE) and isinstance(self.mlp.experts[0].fc_1, nn.Linear):
+            # (refused at the prefill already, not at the first decode step: generation needs the 4-bit expert kernels)
+            raise NotImplementedError("LLaMAMoE on the MI355X needs bias-free QuantLinear experts of one format for "
+                                      "generation (the KV-cache forward); unquantized experts serve only the no-cache "
+                                      "multi-row forward that scoring uses")
         # The norms ride the qkv / fc GEMV prologues and the residual adds the out-projection epilogues. Under
         # tensor parallelism (generate/tp.py's all_reduce_output hook on attn / mlp) the projections yield partial
         # sums: the module then runs without its hook and the reduction + residual add is one fused kernel
@@ -235,7 +240,7 @@ class CausalSelfAttention(nn.Module):
         if input_pos is None:
             # no cache (training-style causal forward, model.py:510-513): a private cache of T rows
             pos = torch.arange(T, device=dev, dtype=torch.int64)
-            kc = torch.empty(G, T, hs, dtype=torch.bfloat16, device=dev)
+            kc = torch.empty(G, T, hs, dtype=qkv.dtype, device=dev)  # bf16, or fp32 under --precision 32-true
             vc = torch.empty_like(kc)
             rope_pos = pos
         else:
@@ -351,6 +356,11 @@ class LLaMAMoE(nn.Module):
     launches (fc_1||fc_2 + SwiGLU, proj); shapes the grouped kernel does not take fall back to the per-expert loop. Forward hooks registered on the experts (``generate/tp.py`` registers the TP
     all-reduce on each expert, tp.py:58-62) are applied to the stacked (T, k, C) expert outputs: a per-element
     sum over ranks, identical to reducing every expert call separately.
+
+    Experts are 4-bit ``QuantLinear`` modules everywhere generation goes (every kernel named above streams packed
+    weights; ``Block.forward`` refuses a KV-cache forward otherwise). The one exception is scoring an unquantized model
+    (lit_gpt/score.py): with ``nn.Linear`` bf16 experts a multi-row input (T > 1) takes the per-expert loop on the bf16
+    GEMM kernels; a single row still raises.
     """
 
     def __init__(self, config: Config) -> None:
@@ -412,8 +422,12 @@ class LLaMAMoE(nn.Module):
         lead, C = x.shape[:-1], x.shape[-1]
         x2 = x.reshape(-1, C).contiguous()
         T, k, E = x2.size(0), c.n_expert_per_token, c.n_expert
-        (q1, s1), (q2, s2), (qp, sp) = self._stack()
         f1, pj = self.experts[0].fc_1, self.experts[0].proj
+        # unquantized (bf16 nn.Linear) experts: multi-row inputs only, through the per-expert loop below — what
+        # scoring a bf16 model needs (lit_gpt/score.py); the one-token decode kernels stream 4-bit experts
+        plain = T > 1 and all(isinstance(l, nn.Linear) for ex in self.experts for l in (ex.fc_1, ex.fc_2, ex.proj))
+        if not plain:
+            (q1, s1), (q2, s2), (qp, sp) = self._stack()
         res = None if residual is None else residual.reshape(T, C).contiguous()
         if T == 1:
             fuse_norm = norm is not None and f1.gemv_fuses_norm(dual=True)
@@ -443,7 +457,7 @@ class LLaMAMoE(nn.Module):
             n = x2 if norm is None else norm(x2)
             router = _lin(self.gate, n)
             ids, probs = ops.moe_route(router.contiguous(), k)
-            if self._grouped_ok(C):
+            if not plain and self._grouped_ok(C):
                 # the reference's per-expert token groups (model.py:740-742) as two grouped launches over a
                 # device-built tile table: no torch.where host sync, no gathered / scattered copies
                 rows, bm = T * k, ops.moe_grouped_bm(T * k)

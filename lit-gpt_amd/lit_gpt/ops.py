@@ -112,6 +112,9 @@ SIGNATURES = {
                               _P],
     "lga_q4_gemv_allreduce_tagged": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(_P), _I, _I, _I, _P, _P,
                                      _P, _P],
+    "lga_token_logprobs": [_P, _I, _I, _P, _P, _P, _P],
+    "lga_token_logprobs_f32": [_P, _I, _I, _P, _P, _P, _P],
+    "lga_logits_kl": [_P, _P, _I, _I, _P, _P, _P],
 }
 _RESTYPES = {"lga_q4_gemv_experts_pair_counters": ctypes.c_size_t, "lga_q4f_workspace_bytes": ctypes.c_size_t, "lga_last_error_string": ctypes.c_char_p, "lga_attention_workspace_bytes": ctypes.c_size_t,
              "lga_comm_mailbox_bytes": ctypes.c_size_t, "lga_q4_gemv_argmax_work_bytes": ctypes.c_size_t}
@@ -775,6 +778,51 @@ def sample_topk(logits, top_k, temperature, *, uniform=None, seed=0, counter=Non
         _opt(table, "table", torch.bfloat16), C, V, _opt(emb_out, "emb_out", torch.bfloat16),
         _opt(kept_out, "kept_out", torch.int32), _opt(probs_out, "probs_out", torch.bfloat16), _stream()))
     return idx
+
+
+# ------------------------------------------------------------------------------------------------ scoring
+def _rows(logits: torch.Tensor, name: str):
+    if logits.dim() != 2 or logits.numel() == 0:
+        raise ValueError(f"{name}: expected non-empty (rows, n) logits, got {tuple(logits.shape)}")
+    return logits.shape
+
+
+def token_logprobs(logits, targets, *, logprob_out=None, argmax_out=None):
+    """(rows, n) bf16 or fp32 logits, (rows,) int32 targets -> (logprob fp32 (rows,), argmax int32 (rows,)):
+    log_softmax(logits)[r, targets[r]] and torch.argmax of each row, one pass over the logits on the device
+    (csrc/score.hip). A target outside [0, n) scores NaN."""
+    rows, n = _rows(logits, "token_logprobs")
+    if targets.numel() != rows:
+        raise ValueError(f"token_logprobs: {targets.numel()} targets for {rows} rows")
+    lp = logprob_out if logprob_out is not None else torch.empty(rows, dtype=torch.float32, device=logits.device)
+    am = argmax_out if argmax_out is not None else torch.empty(rows, dtype=torch.int32, device=logits.device)
+    if lp.numel() != rows or am.numel() != rows:
+        raise ValueError(f"token_logprobs: outputs must hold {rows} elements")
+    if logits.dtype == torch.float32:
+        fn, dt = load_library().lga_token_logprobs_f32, torch.float32
+    elif logits.dtype == torch.bfloat16:
+        fn, dt = load_library().lga_token_logprobs, torch.bfloat16
+    else:
+        raise TypeError(f"token_logprobs: logits must be bf16 or fp32, got {logits.dtype}")
+    _check(fn(_dev(logits, "logits", dt), rows, n, _dev(targets, "targets", torch.int32),
+              _dev(lp, "logprob_out", torch.float32), _dev(am, "argmax_out", torch.int32), _stream()))
+    return lp, am
+
+
+def logits_kl(p, q, *, kl_out=None, agree_out=None):
+    """Two (rows, n) bf16 logit matrices -> (kl fp32 (rows,), agree int32 (rows,)): KL(softmax(p) || softmax(q)) per
+    row (not clamped) and whether the rows' argmax agree, one pass over both (csrc/score.hip)."""
+    rows, n = _rows(p, "logits_kl")
+    if tuple(q.shape) != (rows, n):
+        raise ValueError(f"logits_kl: shapes differ {tuple(p.shape)} vs {tuple(q.shape)}")
+    kl = kl_out if kl_out is not None else torch.empty(rows, dtype=torch.float32, device=p.device)
+    ag = agree_out if agree_out is not None else torch.empty(rows, dtype=torch.int32, device=p.device)
+    if kl.numel() != rows or ag.numel() != rows:
+        raise ValueError(f"logits_kl: outputs must hold {rows} elements")
+    _check(load_library().lga_logits_kl(_dev(p, "p", torch.bfloat16), _dev(q, "q", torch.bfloat16), rows, n,
+                                        _dev(kl, "kl_out", torch.float32), _dev(ag, "agree_out", torch.int32),
+                                        _stream()))
+    return kl, ag
 
 
 # ------------------------------------------------------------------------------------------------ sparse MoE
