@@ -66,6 +66,18 @@ int lga_q4_gemv(const void* x, const uint8_t* qweight, const void* scales, const
 int lga_q4_gemv_swiglu(const void* x, const uint8_t* qweight1, const void* scales1, const uint8_t* qweight2,
                        const void* scales2, const void* norm_weight, float norm_eps, void* y, int N, int K,
                        int group, int fmt, int variant, lga_stream_t stream);
+/* -- batched decode GEMV, 1 <= M <= 8 rows (one token of each sequence of a decode batch; the reference's
+ *    set_kv_cache(batch_size) / idx (B, 1) forward) ----------------------------------------------------------
+ * y[M][N] from x[M][K] (residual[M][N]): the packed weights are streamed ONCE and dotted against every row while
+ * they sit in registers. Row r of y is bit-identical to lga_q4_gemv (lga_q4_gemv_swiglu) on x[r], residual[r]
+ * with variant -1, for every M and r: the launch takes the one-row geometry and its per-row arithmetic. Fused
+ * RMSNorm: K <= 8192 (K <= 4096 for the SwiGLU pair). */
+int lga_q4_gemv_rows(const void* x, const uint8_t* qweight, const void* scales, const void* bias,
+                     const void* residual, const void* norm_weight, float norm_eps, void* y, int M, int N, int K,
+                     int group, int fmt, lga_stream_t stream);
+int lga_q4_gemv_swiglu_rows(const void* x, const uint8_t* qweight1, const void* scales1, const uint8_t* qweight2,
+                            const void* scales2, const void* norm_weight, float norm_eps, void* y, int M, int N,
+                            int K, int group, int fmt, lga_stream_t stream);
 
 /* -- prefill GEMM, M > 1 (bnb dequantize_4bit + cuBLAS GEMM) -------------------------------------------- */
 int lga_q4_gemm(const void* x, const uint8_t* qweight, const void* scales, const void* bias, const void* residual,

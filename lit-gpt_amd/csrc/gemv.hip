@@ -40,8 +40,23 @@ __global__ void __launch_bounds__(kGemvNW * 64) gemv_q4_kernel(GemvArgs a) {
   gemv_q4_body<RPR, CPT, FMT, DUAL, NORM, RES, kGemvNW>(a, blockIdx.x, smem);
 }
 
-template <int RPR, int CPT, int FMT, bool DUAL>
-static void launch(const GemvArgs& a, hipStream_t stream) {
+// the same geometry over M activation rows (lga_q4_gemv*_rows): gemv_q4_body's ROWS form
+template <int RPR, int CPT, int FMT, bool DUAL, bool NORM, bool RES>
+__global__ void __launch_bounds__(kGemvNW * 64) gemv_q4_rows_kernel(GemvArgs a, int M) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  gemv_q4_body<RPR, CPT, FMT, DUAL, NORM, RES, kGemvNW, false, true>(a, blockIdx.x, smem, M);
+}
+
+// ROWS: the launchers below pick the multi-row kernel of the SAME geometry, so dispatch() is the one geometry table
+// of lga_q4_gemv* and lga_q4_gemv*_rows
+#define LGA_GEMV_K(NORM, RES)                                                                     \
+  do {                                                                                            \
+    if constexpr (ROWS) gemv_q4_rows_kernel<RPR, CPT, FMT, DUAL, NORM, RES><<<blocks, NT, lds, stream>>>(a, M); \
+    else gemv_q4_kernel<RPR, CPT, FMT, DUAL, NORM, RES><<<blocks, NT, lds, stream>>>(a);          \
+  } while (0)
+
+template <int RPR, int CPT, int FMT, bool DUAL, bool ROWS = false>
+static void launch(const GemvArgs& a, hipStream_t stream, int M = 1) {
   const int waves = (a.N + RPR - 1) / RPR;
   const dim3 blocks((waves + kGemvNW - 1) / kGemvNW, a.eidx ? a.slots : 1);
   size_t lds = (size_t)a.K * 2 + (a.K / 32) * 4 + 16 * 4 + 16 * 4;
@@ -51,21 +66,28 @@ static void launch(const GemvArgs& a, hipStream_t stream) {
   constexpr int NT = kGemvNW * 64;
   const bool norm = a.norm_w != nullptr, res = a.residual != nullptr;
   if (DUAL) {
-    if (norm) gemv_q4_kernel<RPR, CPT, FMT, DUAL, true, false><<<blocks, NT, lds, stream>>>(a);
-    else gemv_q4_kernel<RPR, CPT, FMT, DUAL, false, false><<<blocks, NT, lds, stream>>>(a);
+    if (norm) LGA_GEMV_K(true, false);
+    else LGA_GEMV_K(false, false);
   } else if (norm) {
-    if (res) gemv_q4_kernel<RPR, CPT, FMT, DUAL, true, true><<<blocks, NT, lds, stream>>>(a);
-    else gemv_q4_kernel<RPR, CPT, FMT, DUAL, true, false><<<blocks, NT, lds, stream>>>(a);
+    if (res) LGA_GEMV_K(true, true);
+    else LGA_GEMV_K(true, false);
   } else {
-    if (res) gemv_q4_kernel<RPR, CPT, FMT, DUAL, false, true><<<blocks, NT, lds, stream>>>(a);
-    else gemv_q4_kernel<RPR, CPT, FMT, DUAL, false, false><<<blocks, NT, lds, stream>>>(a);
+    if (res) LGA_GEMV_K(false, true);
+    else LGA_GEMV_K(false, false);
   }
 }
+#undef LGA_GEMV_K
 
 template <int RT, int CPT, int FMT, bool DUAL, bool NORM, bool RES>
 __global__ void __launch_bounds__(256) gemv_q4s_kernel(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   gemv_q4_stream<RT, CPT, FMT, DUAL, NORM, RES>(a, smem);
+}
+
+template <int RT, int CPT, int FMT, bool DUAL, bool NORM, bool RES>
+__global__ void __launch_bounds__(256) gemv_q4s_rows_kernel(GemvArgs a, int M) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  gemv_q4_stream<RT, CPT, FMT, DUAL, NORM, RES, false, true>(a, smem, AmaxArgs{}, M);
 }
 
 // greedy decode head: RMSNorm + lm_head GEMV (streaming form) + argmax + next-token embedding in one launch
@@ -81,34 +103,44 @@ static int amax_grid(int N, int K) {  // the streaming form's grid for a plain G
 }
 
 // streaming form (variant bit 2): RT rows per tile, `wpc` workgroups per CU (variant bits 4..7, default 2)
-template <int RT, int CPT, int FMT, bool DUAL>
-static void launch_stream(const GemvArgs& a, int wpc, hipStream_t stream) {
+#define LGA_GEMV_S(NORM, RES)                                                                      \
+  do {                                                                                             \
+    if constexpr (ROWS) gemv_q4s_rows_kernel<RT, CPT, FMT, DUAL, NORM, RES><<<blocks, 256, lds, stream>>>(a, M); \
+    else gemv_q4s_kernel<RT, CPT, FMT, DUAL, NORM, RES><<<blocks, 256, lds, stream>>>(a);          \
+  } while (0)
+
+template <int RT, int CPT, int FMT, bool DUAL, bool ROWS = false>
+static void launch_stream(const GemvArgs& a, int wpc, hipStream_t stream, int M = 1) {
   const int tiles = (a.N + RT - 1) / RT;
+  // ROWS: all M rows staged at once (<= 70 KB at K = 4096); the grid never asks for more workgroups per CU than
+  // that footprint lets reside (160 KiB of LDS per CU): 3 up to six rows of K = 4096, 2 above
+  const size_t lds = ROWS ? gemv_rows_stream_lds(a.K, M) : (size_t)a.K * 2 + (a.K / 32) * 4 + 16 * 4 + 16 * 4;
+  if (ROWS) wpc = max(1, min(wpc, (int)(163840 / lds)));
   const int blocks = max(1, min(num_cu() * wpc, (tiles + 3) / 4));
-  const size_t lds = (size_t)a.K * 2 + (a.K / 32) * 4 + 16 * 4 + 16 * 4;
   const bool norm = a.norm_w != nullptr, res = a.residual != nullptr;
   if (DUAL) {
-    if (norm) gemv_q4s_kernel<RT, CPT, FMT, true, true, false><<<blocks, 256, lds, stream>>>(a);
-    else gemv_q4s_kernel<RT, CPT, FMT, true, false, false><<<blocks, 256, lds, stream>>>(a);
+    if (norm) LGA_GEMV_S(true, false);
+    else LGA_GEMV_S(false, false);
   } else if (norm) {
-    if (res) gemv_q4s_kernel<RT, CPT, FMT, false, true, true><<<blocks, 256, lds, stream>>>(a);
-    else gemv_q4s_kernel<RT, CPT, FMT, false, true, false><<<blocks, 256, lds, stream>>>(a);
+    if (res) LGA_GEMV_S(true, true);
+    else LGA_GEMV_S(true, false);
   } else {
-    if (res) gemv_q4s_kernel<RT, CPT, FMT, false, false, true><<<blocks, 256, lds, stream>>>(a);
-    else gemv_q4s_kernel<RT, CPT, FMT, false, false, false><<<blocks, 256, lds, stream>>>(a);
+    if (res) LGA_GEMV_S(false, true);
+    else LGA_GEMV_S(false, false);
   }
 }
+#undef LGA_GEMV_S
 
 // The streaming form pays off for tall matrices over short rows (tools/gemv_variants.py, Llama-2-7B shapes):
 // fc_1 || fc_2 (2 x 11008 x 4096) 10.9 vs 12.2 us, lm_head (32000 x 4096) 14.3 vs 15.9 us at 3 workgroups per
 // CU; not for qkv / o_proj / mlp.proj (equal or slower). Instantiated for K <= 4096 only.
-template <int FMT, bool DUAL>
-static int dispatch_stream(const GemvArgs& a, int variant, hipStream_t stream) {
+template <int FMT, bool DUAL, bool ROWS = false>
+static int dispatch_stream(const GemvArgs& a, int variant, hipStream_t stream, int M = 1) {
   const int cpt = (a.K / 32 + 63) / 64;
   const int wpc = (variant >> 4) & 15 ? (variant >> 4) & 15 : (DUAL ? 2 : 3);
   switch (cpt) {
-    case 1: launch_stream<(DUAL ? 1 : 2), 1, FMT, DUAL>(a, wpc, stream); break;
-    case 2: launch_stream<(DUAL ? 1 : 2), 2, FMT, DUAL>(a, wpc, stream); break;
+    case 1: launch_stream<(DUAL ? 1 : 2), 1, FMT, DUAL, ROWS>(a, wpc, stream, M); break;
+    case 2: launch_stream<(DUAL ? 1 : 2), 2, FMT, DUAL, ROWS>(a, wpc, stream, M); break;
     default:
       lga_set_error("lga_q4_gemv: the streaming form covers K <= 4096");
       return (int)hipErrorInvalidValue;
@@ -121,12 +153,13 @@ static bool stream_default(int N, int K, bool dual) {
 }
 
 // variant: 0 = fewer rows per wave (more waves), 1 = more rows per wave; < 0 = heuristic
-template <int FMT, bool DUAL>
-static int dispatch(const GemvArgs& a, int variant, hipStream_t stream) {
+// ROWS: the M-row launch (lga_q4_gemv*_rows) of the geometry this function picks for one row
+template <int FMT, bool DUAL, bool ROWS = false>
+static int dispatch(const GemvArgs& a, int variant, hipStream_t stream, int M = 1) {
   const int cpt = (a.K / 32 + 63) / 64;  // chunks per lane (== uint4 of x per thread)
   if (!a.eidx && a.K <= 4096 &&
       ((variant >= 0 && (variant & 4)) || (variant < 0 && stream_default(a.N, a.K, DUAL))))
-    return dispatch_stream<FMT, DUAL>(a, variant < 0 ? 4 : variant, stream);
+    return dispatch_stream<FMT, DUAL, ROWS>(a, variant < 0 ? 4 : variant, stream, M);
   if (variant < 0) {
     const long rows = DUAL ? 2L * a.N : a.N;
     variant = rows >= 24000 ? 1 : 0;  // tall matrices: more rows per wave keep the grid ~3-4 workgroups per CU
@@ -147,9 +180,9 @@ static int dispatch(const GemvArgs& a, int variant, hipStream_t stream) {
   const bool half = (variant & 8) != 0;  // half the small variant's rows per wave (bit 3)
 #define LGA_L(RS, RB, CPT)                                                         \
   do {                                                                             \
-    if (big) launch<(DUAL ? (RB) / 2 : (RB)), CPT, FMT, DUAL>(a, stream);          \
-    else if (half) launch<((RS) >= 4 ? (DUAL ? (RS) / 4 : (RS) / 2) : (DUAL ? (RS) / 2 : (RS))), CPT, FMT, DUAL>(a, stream); \
-    else launch<(DUAL ? (RS) / 2 : (RS)), CPT, FMT, DUAL>(a, stream);              \
+    if (big) launch<(DUAL ? (RB) / 2 : (RB)), CPT, FMT, DUAL, ROWS>(a, stream, M); \
+    else if (half) launch<((RS) >= 4 ? (DUAL ? (RS) / 4 : (RS) / 2) : (DUAL ? (RS) / 2 : (RS))), CPT, FMT, DUAL, ROWS>(a, stream, M); \
+    else launch<(DUAL ? (RS) / 2 : (RS)), CPT, FMT, DUAL, ROWS>(a, stream, M);     \
   } while (0)
   switch (cpt) {
     case 1: LGA_L(4, 8, 1); break;
@@ -209,6 +242,44 @@ extern "C" int lga_q4_gemv_swiglu(const void* x, const uint8_t* qweight1, const 
                   (const uint16_t*)norm_weight, (uint16_t*)y, N, K, group, norm_eps};
   a.cb = lga::codebook_of(fmt);
   const int rc = fmt == 0 ? lga::dispatch<0, true>(a, variant, stream) : lga::dispatch<1, true>(a, variant, stream);
+  if (rc) return rc;
+  LGA_LAUNCH_RETURN();
+}
+
+// Batched decode (one token of each sequence of a batch): M = 1..8 activation rows against one pass over the packed
+// weights. Row r of y has the bits lga_q4_gemv(_swiglu) writes for x[r] (residual[r]) with variant -1: dispatch()
+// picks the one-row geometry and launches its ROWS kernel.
+extern "C" int lga_q4_gemv_rows(const void* x, const uint8_t* qweight, const void* scales, const void* bias,
+                                const void* residual, const void* norm_weight, float norm_eps, void* y, int M, int N,
+                                int K, int group, int fmt, hipStream_t stream) {
+  LGA_CHECK_ARG(x && qweight && scales && y, "lga_q4_gemv_rows: null pointer");
+  LGA_CHECK_ARG(M >= 1 && M <= 8, "lga_q4_gemv_rows: M must be 1..8 rows");
+  LGA_CHECK_ARG(N > 0 && K > 0 && K % 32 == 0, "lga_q4_gemv_rows: K must be a positive multiple of 32");
+  LGA_CHECK_ARG(group >= 32 && group % 32 == 0 && K % group == 0, "lga_q4_gemv_rows: group must be a multiple of 32 dividing K");
+  LGA_CHECK_ARG(fmt == 0 || fmt == 1 || fmt == 3, "lga_q4_gemv_rows: fmt must be 0 (int4-g), 1 (nf4) or 3 (fp4)");
+  LGA_CHECK_ARG(!norm_weight || K / 32 <= 256, "lga_q4_gemv_rows: fused RMSNorm needs K <= 8192");
+  lga::GemvArgs a{(const uint16_t*)x, qweight, scales, nullptr, nullptr, (const uint16_t*)bias,
+                  (const uint16_t*)residual, (const uint16_t*)norm_weight, (uint16_t*)y, N, K, group, norm_eps};
+  a.cb = lga::codebook_of(fmt);
+  const int rc = fmt == 0 ? lga::dispatch<0, false, true>(a, -1, stream, M) : lga::dispatch<1, false, true>(a, -1, stream, M);
+  if (rc) return rc;
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_q4_gemv_swiglu_rows(const void* x, const uint8_t* qweight1, const void* scales1,
+                                       const uint8_t* qweight2, const void* scales2, const void* norm_weight,
+                                       float norm_eps, void* y, int M, int N, int K, int group, int fmt,
+                                       hipStream_t stream) {
+  LGA_CHECK_ARG(x && qweight1 && scales1 && qweight2 && scales2 && y, "lga_q4_gemv_swiglu_rows: null pointer");
+  LGA_CHECK_ARG(M >= 1 && M <= 8, "lga_q4_gemv_swiglu_rows: M must be 1..8 rows");
+  LGA_CHECK_ARG(N > 0 && K > 0 && K % 32 == 0, "lga_q4_gemv_swiglu_rows: K must be a positive multiple of 32");
+  LGA_CHECK_ARG(group >= 32 && group % 32 == 0 && K % group == 0, "lga_q4_gemv_swiglu_rows: bad group");
+  LGA_CHECK_ARG(fmt == 0 || fmt == 1 || fmt == 3, "lga_q4_gemv_swiglu_rows: fmt must be 0, 1 or 3");
+  LGA_CHECK_ARG(!norm_weight || K / 32 <= 128, "lga_q4_gemv_swiglu_rows: fused RMSNorm needs K <= 4096");
+  lga::GemvArgs a{(const uint16_t*)x, qweight1, scales1, qweight2, scales2, nullptr, nullptr,
+                  (const uint16_t*)norm_weight, (uint16_t*)y, N, K, group, norm_eps};
+  a.cb = lga::codebook_of(fmt);
+  const int rc = fmt == 0 ? lga::dispatch<0, true, true>(a, -1, stream, M) : lga::dispatch<1, true, true>(a, -1, stream, M);
   if (rc) return rc;
   LGA_LAUNCH_RETURN();
 }

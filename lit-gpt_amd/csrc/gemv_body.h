@@ -57,8 +57,20 @@ __device__ __forceinline__ uint16_t* gemv_out_lds(unsigned char* smem, int K) { 
 // One wave of a decode GEMV (see gemv.hip for the design). NW waves per workgroup (each its own row slot); the
 // workgroup stages x once for all of them. LDS_OUT (gemv_ar.hip): the workgroup's NW * RPR bf16 rows go to LDS
 // (gemv_out_lds) instead of a.y, for an epilogue that moves them on as 16-B pieces.
-template <int RPR, int CPT, int FMT, bool DUAL, bool NORM, bool RES, int NW = 4, bool LDS_OUT = false>
-__device__ __forceinline__ void gemv_q4_body(GemvArgs a, int blk, unsigned char* smem) {
+// ROWS (lga_q4_gemv*_rows, batched decode): `rows` activation rows (x [rows][K], residual / y [rows][N]) against the
+// SAME register-resident weights. The
+// wave's weight loads are issued once; steps 3 and 4 then run once per activation row m (x + m K staged into the
+// one-row LDS area, so the footprint and the occupancy are the one-row kernel's; y + m N, residual + m N), the next
+// row's x fetched while this one is computed (up to 8 chunks per lane; above — K > 16384 — the registers do not take
+// an x share next to the weights for the whole loop, and every row's x, the first one's too, is fetched when its turn
+// comes, after the weight loads). Each row goes through exactly the one-row code below, so row m's
+// output has the bits of a one-row launch on x[m].
+template <int RPR, int CPT, int FMT, bool DUAL, bool NORM, bool RES, int NW = 4, bool LDS_OUT = false,
+          bool ROWS = false>
+__device__ __forceinline__ void gemv_q4_body(GemvArgs a, int blk, unsigned char* smem, int rows = 1) {
+  static_assert(!ROWS || !LDS_OUT, "ROWS writes a.y");
+  constexpr bool AHEAD = ROWS && CPT <= 8;  // the next row's x is fetched during this row's work
+  constexpr bool HIDE_IN_PLACE = ROWS && !(DUAL && CPT > 8);  // how step 4 keeps the unpacking in the row loop
   if (a.eidx) {  // wave-uniform: one scalar load of the routed expert id, then plain pointer offsets
     const long long e = min(max(a.eidx[blockIdx.y], 0), a.n_expert - 1);
     a.qw += e * a.ew;
@@ -88,6 +100,7 @@ __device__ __forceinline__ void gemv_q4_body(GemvArgs a, int blk, unsigned char*
   uint4 xr[XI], nr[XI];
 #pragma unroll
   for (int i = 0; i < XI; ++i) {
+    if constexpr (ROWS && !AHEAD) break;  // (fetched per row, below)
     const int u = min(t + NT * i, n8 - 1);
 #ifdef LGA_LAB_NOX  // lab builds only: cost of the activation fetch
     xr[i] = make_uint4(0x3F803F80u + u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);
@@ -130,6 +143,24 @@ __device__ __forceinline__ void gemv_q4_body(GemvArgs a, int blk, unsigned char*
   __builtin_amdgcn_sched_barrier(0);  // nothing that waits on x may move above the weight loads
   LGA_GTRACE_NOWAIT(1);
 
+  const int M = ROWS ? rows : 1;
+  for (int m = 0; m < M; ++m) {
+  uint4 xn[AHEAD ? XI : 1];  // AHEAD: the next activation row (and its residual), in flight during this row's work
+  uint32_t resn = 0;
+  if constexpr (AHEAD) {
+    const size_t mn = (size_t)min(m + 1, M - 1);
+#pragma unroll
+    for (int i = 0; i < XI; ++i) xn[AHEAD ? i : 0] = ((const uint4*)(a.x + mn * a.K))[min(t + NT * i, n8 - 1)];
+    if (RES) resn = a.residual[mn * a.N + min(row0 + (lane & (RPR - 1)), a.N - 1)];
+  } else if constexpr (ROWS) {
+#pragma unroll
+    for (int i = 0; i < XI; ++i) {
+      const int u = min(t + NT * i, n8 - 1);
+      xr[i] = ((const uint4*)(a.x + (size_t)m * a.K))[u];
+      if (NORM) nr[i] = ((const uint4*)a.norm_w)[u];
+    }
+    if (RES) res = a.residual[(size_t)m * a.N + min(row0 + (lane & (RPR - 1)), a.N - 1)];
+  }
   // 3. stage x into LDS (RMS-normalised when NORM) while the weights stream
   float rs = 1.0f;
   if (NORM) {
@@ -193,6 +224,26 @@ __device__ __forceinline__ void gemv_q4_body(GemvArgs a, int blk, unsigned char*
     const int cc = min(c, NC - 1);
     const uint4* xc = xl + cc * 4;
     const float xs = xsum[cc];
+    if constexpr (ROWS) {
+      // the weights do not change over the activation rows: left visible, the compiler hoists their unpacking out
+      // of the row loop and holds every unpacked value live (hundreds of registers, spilled to scratch)
+      // (HIDE_IN_PLACE: the operands pin the weights to architectural VGPRs for the whole loop; the dual launch at
+      // more than 8 chunks per lane — 160 weight and scale registers — has no room for that next to the x staging,
+      // so step 4 hides a copy of each chunk there instead, four moves per chunk and row)
+      if constexpr (HIDE_IN_PLACE) {
+#pragma unroll
+        for (int i = 0; i < RPR; ++i) {
+          asm volatile("" : "+v"(w[i][j].x), "+v"(w[i][j].y), "+v"(w[i][j].z), "+v"(w[i][j].w), "+v"(s[i][j]));
+          if (DUAL)
+            asm volatile("" : "+v"(w2[DUAL ? i : 0][DUAL ? j : 0].x), "+v"(w2[DUAL ? i : 0][DUAL ? j : 0].y),
+                         "+v"(w2[DUAL ? i : 0][DUAL ? j : 0].z), "+v"(w2[DUAL ? i : 0][DUAL ? j : 0].w),
+                         "+v"(s2[DUAL ? i : 0][DUAL ? j : 0]));
+        }
+      } else {  // (the scales alone stay hidden in place)
+#pragma unroll
+        for (int i = 0; i < RPR; ++i) asm volatile("" : "+v"(s[i][j]), "+v"(s2[DUAL ? i : 0][DUAL ? j : 0]));
+      }
+    }
 #ifdef LGA_LAB_NOCOMPUTE  // lab builds only: cost of the dequant-dot (weights folded, not multiplied)
 #pragma unroll
     for (int i = 0; i < RPR; ++i) {
@@ -216,6 +267,10 @@ __device__ __forceinline__ void gemv_q4_body(GemvArgs a, int blk, unsigned char*
       } else {
         wj[i] = w[i][j];
       }
+    }
+    if constexpr (ROWS && !HIDE_IN_PLACE) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) asm volatile("" : "+v"(wj[r].x), "+v"(wj[r].y), "+v"(wj[r].z), "+v"(wj[r].w));
     }
     float d[R];
     chunk_dot_rows<FMT, R>(wj, xc, xs, nf4, nmask, nmagic, nmask_hi, d);
@@ -262,6 +317,16 @@ __device__ __forceinline__ void gemv_q4_body(GemvArgs a, int blk, unsigned char*
     }
     LGA_GTRACE(5);
   }
+  if constexpr (ROWS) {
+    __syncthreads();  // every wave is done with this row's LDS before the next one is staged
+    if constexpr (AHEAD) {
+#pragma unroll
+      for (int i = 0; i < XI; ++i) xr[i] = xn[AHEAD ? i : 0];
+      res = resn;
+    }
+    a.y += a.N;
+  }
+  }  // activation rows
 }
 
 }  // namespace lga

@@ -44,16 +44,28 @@ __device__ __forceinline__ void amax_take(float v, int i, float& bv, int& bi) {
   bi = t ? i : bi;
 }
 
-template <int RT, int CPT, int FMT, bool DUAL, bool NORM, bool RES, bool AMAX = false>
-__device__ __forceinline__ void gemv_q4_stream(GemvArgs a, unsigned char* smem, AmaxArgs am = AmaxArgs{}) {
+// LDS bytes of one staged activation row in the ROWS form (x pairs + chunk sums, 16-B aligned) and of the launch
+__host__ __device__ inline size_t gemv_rows_stride(int K) { return ((size_t)K * 2 + (K / 32) * 4 + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t gemv_rows_stream_lds(int K, int M) { return gemv_rows_stride(K) * M + 16 * 4 + 16 * 4; }
+
+// ROWS (lga_q4_gemv*_rows, batched decode): all `rows` activation rows are staged up front (row m at m *
+// gemv_rows_stride(K); K <= 4096, so at most 70 KB), and every weight tile is dotted against each of them while it
+// sits in registers — the same chunk_dot_rows / butterfly / epilogue per row, so row m has the bits of a one-row
+// launch on x[m].
+template <int RT, int CPT, int FMT, bool DUAL, bool NORM, bool RES, bool AMAX = false, bool ROWS = false>
+__device__ __forceinline__ void gemv_q4_stream(GemvArgs a, unsigned char* smem, AmaxArgs am = AmaxArgs{},
+                                               int rows = 1) {
   static_assert(!AMAX || (!DUAL && !RES), "AMAX: a plain (lm_head) GEMV");
+  static_assert(!AMAX || !ROWS, "AMAX: one row");
   constexpr int NW = 4, NT = NW * 64;
   constexpr int XI = (CPT * 4 + NW - 1) / NW;
   using Tile = GemvTile<RT, CPT, FMT, DUAL>;
   constexpr int R = Tile::R;
+  const int M = ROWS ? rows : 1;
+  const size_t xstride = ROWS ? gemv_rows_stride(a.K) : 0;
   uint4* xl = (uint4*)smem;
   float* xsum = (float*)(smem + (size_t)a.K * 2);
-  float* red = xsum + a.K / 32;
+  float* red = ROWS ? (float*)(smem + xstride * M) : xsum + a.K / 32;
   float* nf4 = red + 16;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
   const int NC = a.K / 32, n8 = a.K / 8, groups = a.K / a.G;
@@ -91,7 +103,7 @@ __device__ __forceinline__ void gemv_q4_stream(GemvArgs a, unsigned char* smem, 
         }
       }
     }
-    if (RES) b.res = a.residual[live ? min(tile * RT + (RT > 1 ? (lane & (RT - 1)) : 0), a.N - 1) : 0];
+    if (RES && !ROWS) b.res = a.residual[live ? min(tile * RT + (RT > 1 ? (lane & (RT - 1)) : 0), a.N - 1) : 0];
   };
   Tile A, B;
   issue(A, gw);
@@ -99,6 +111,13 @@ __device__ __forceinline__ void gemv_q4_stream(GemvArgs a, unsigned char* smem, 
   __builtin_amdgcn_sched_barrier(0);
 
   // 3. stage x (RMS-normalised when NORM) into LDS while the first tiles stream (gemv_q4_body step 3)
+  for (int m = 0; m < M; ++m) {
+  uint4 xn[ROWS ? XI : 1];  // ROWS: the next activation row, fetched while this one is staged
+  if constexpr (ROWS) {
+    const size_t mn = (size_t)min(m + 1, M - 1);
+#pragma unroll
+    for (int i = 0; i < XI; ++i) xn[ROWS ? i : 0] = ((const uint4*)(a.x + mn * a.K))[min(t + NT * i, n8 - 1)];
+  }
   float rs = 1.0f;
   if (NORM) {
     float ss = 0.0f;
@@ -140,12 +159,27 @@ __device__ __forceinline__ void gemv_q4_stream(GemvArgs a, unsigned char* smem, 
     }
   }
   __syncthreads();
+  if constexpr (ROWS) {  // on to the next row's LDS area (the barrier above also frees `red` for its sum of squares)
+#pragma unroll
+    for (int i = 0; i < XI; ++i) xr[i] = xn[ROWS ? i : 0];
+    xl = (uint4*)((unsigned char*)xl + xstride);
+    xsum = (float*)((unsigned char*)xsum + xstride);
+  }
+  }  // activation rows
+  if constexpr (ROWS) {
+    xl = (uint4*)smem;
+    xsum = (float*)(smem + (size_t)a.K * 2);
+  }
 
   // 4. tile loop: dot + butterfly + epilogue of tile k, then issue tile k + 2 into the freed buffer
   const uint32_t nmask = nibble_mask(), nmagic = f16_magic(), nmask_hi = nibble_mask_hi();
   float abv = -INFINITY;  // AMAX: this lane's best (value, row)
   int abi = 0x7FFFFFFF;
-  auto consume = [&](const Tile& b, int tile) {
+  auto consume = [&](Tile& b, int tile) {
+   for (int m = 0; m < M; ++m) {  // ROWS: every staged activation row against this tile's registers
+    const uint4* xl_m = (const uint4*)((const unsigned char*)xl + xstride * m);
+    const float* xsum_m = (const float*)((const unsigned char*)xsum + xstride * m);
+    uint16_t* y_m = a.y + (size_t)m * a.N;
     float part[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) part[r] = 0.0f;
@@ -156,9 +190,13 @@ __device__ __forceinline__ void gemv_q4_stream(GemvArgs a, unsigned char* smem, 
       const int cc = min(c, NC - 1);
       uint4 wj[R];
 #pragma unroll
-      for (int r = 0; r < R; ++r) wj[r] = b.w[r][j];
+      for (int r = 0; r < R; ++r) {
+        // (ROWS: the tile does not change over the activation rows; keep its unpacking inside the row loop)
+        if constexpr (ROWS) asm volatile("" : "+v"(b.w[r][j].x), "+v"(b.w[r][j].y), "+v"(b.w[r][j].z), "+v"(b.w[r][j].w), "+v"(b.s[r][j]));
+        wj[r] = b.w[r][j];
+      }
       float d[R];
-      chunk_dot_rows<FMT, R>(wj, xl + cc * 4, xsum[cc], nf4, nmask, nmagic, nmask_hi, d);
+      chunk_dot_rows<FMT, R>(wj, xl_m + cc * 4, xsum_m[cc], nf4, nmask, nmagic, nmask_hi, d);
 #pragma unroll
       for (int r = 0; r < R; ++r) part[r] = fmaf(ok ? scale_of<FMT>(b.s[r][j]) : 0.0f, d[r], part[r]);
     }
@@ -179,22 +217,27 @@ __device__ __forceinline__ void gemv_q4_stream(GemvArgs a, unsigned char* smem, 
       const int row = row0 + (vi >> 1);
       const float gs = round_bf(silu_f(round_bf(tot)));
       const uint16_t ob = f2bf(__fmul_rn(gs, round_bf(other)));
-      if ((lane & (GROUP - 1)) == 0 && (vi & 1) == 0 && tile < T && row < a.N) a.y[row] = ob;
+      if ((lane & (GROUP - 1)) == 0 && (vi & 1) == 0 && tile < T && row < a.N) y_m[row] = ob;
     } else {
       const int row = row0 + vi;
       float o = tot;
       if (RES) {
+        // (ROWS: row m's residual is read here; the default geometry streams only residual-free shapes)
+        const uint32_t rres = ROWS ? (uint32_t)a.residual[(size_t)m * a.N +
+                                                          min(row0 + (RT > 1 ? (lane & (RT - 1)) : 0), a.N - 1)]
+                                   : b.res;
         o = round_bf(a.bias ? o + bf2f(a.bias[min(row, a.N - 1)]) : o) +
-            __uint_as_float(((uint32_t)__shfl(b.res, vi)) << 16);
+            __uint_as_float(((uint32_t)__shfl(rres, vi)) << 16);
       } else if (a.bias) {
         o += bf2f(a.bias[min(row, a.N - 1)]);
       }
       const uint16_t ob = f2bf(o);
       if ((lane & (GROUP - 1)) == 0 && tile < T && row < a.N) {
-        a.y[row] = ob;
+        y_m[row] = ob;
         if (AMAX) amax_take(bf2f(ob), row, abv, abi);
       }
     }
+   }  // activation rows
   };
   for (int tile = gw; tile < T; tile += 2 * W) {  // wave-uniform trip count
     consume(A, tile);

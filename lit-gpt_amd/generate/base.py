@@ -22,7 +22,7 @@ import argparse
 import sys
 import time
 from pathlib import Path
-from typing import Any, Optional
+from typing import Any, List, Optional
 
 import torch
 
@@ -94,15 +94,17 @@ DECODE_CHUNK = 8  # greedy decode steps per graph launch (lit_gpt/runtime.py Dec
 
 @torch.inference_mode()
 def generate(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
-             top_k: Optional[int] = None, eos_id: Optional[int] = None, use_graph: bool = True) -> torch.Tensor:
-    """Takes a conditioning sequence (prompt, shape (T,)) and continues it; returns (T + new,) ids."""
+             top_k: Optional[int] = None, eos_id: Optional[int] = None, use_graph: bool = True,
+             rng: Optional[SamplerRNG] = None) -> torch.Tensor:
+    """Takes a conditioning sequence (prompt, shape (T,)) and continues it; returns (T + new,) ids. ``rng``: the
+    device sampler's state to draw from (a fresh one seeded from torch's generator when omitted)."""
     T = prompt.size(0)
     assert max_returned_tokens > T
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     device = prompt.device
     tokens = [prompt]
-    rng = SamplerRNG(device) if temperature > 0.0 else None
+    rng = (rng or SamplerRNG(device)) if temperature > 0.0 else None
     token = next_token(model, torch.arange(0, T, device=device), prompt.view(1, -1), temperature=temperature,
                        top_k=top_k, rng=rng).clone()
     tokens.append(token)
@@ -149,6 +151,97 @@ def generate(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, *, temp
         input_pos = input_pos.add_(1)
     _check_collectives()
     return torch.cat(tokens)
+
+
+MAX_BATCH = GPT.MAX_BATCH  # sequences per batched decode step (4: lit_gpt/model.py)
+
+
+def _batch_steps(dg, n_steps: int, eos_id: Optional[int]):
+    """Drive a batched step executor (lit_gpt.runtime.BatchDecodeGraph: ``B``, ``token`` (B,) holding the first
+    step's tokens, ``chunk``, ``step()``, ``steps()``) for ``n_steps`` steps in all. Returns the (n_steps, B) token
+    buffer and, per sequence, how many of its tokens count: up to and including its first ``eos_id``. A sequence
+    that met it stops collecting; the batch keeps stepping until every sequence has, one host read per launch."""
+    B = dg.B
+    out = torch.empty(n_steps, B, dtype=torch.int64, device=dg.token.device)
+    out[0] = dg.token.view(-1)
+    lengths: List[Optional[int]] = [None] * B
+
+    def scan(i: int, n: int) -> bool:  # rows i .. i + n are new: note each open sequence's first eos among them
+        if eos_id is None:
+            return False
+        hit = (out[i:i + n] == eos_id).cpu()  # the launch's one device -> host read
+        for b in range(B):
+            if lengths[b] is None and bool(hit[:, b].any()):
+                lengths[b] = i + int(hit[:, b].nonzero()[0]) + 1
+        return all(n_b is not None for n_b in lengths)
+
+    i = 1
+    done = scan(0, 1)
+    while i < n_steps and not done:
+        if dg.chunk > 1 and n_steps - i >= dg.chunk:
+            out[i:i + dg.chunk] = dg.steps()
+            n = dg.chunk
+        else:
+            out[i] = dg.step().view(-1)
+            n = 1
+        done = scan(i, n)
+        i += n
+    return out, [i if n_b is None else n_b for n_b in lengths]
+
+
+@torch.inference_mode()
+def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
+                   top_k: Optional[int] = None, eos_id: Optional[int] = None, seeds: Optional[List[int]] = None,
+                   use_graph: bool = True) -> List[torch.Tensor]:
+    """Continue up to MAX_BATCH = 4 prompts (each (T_b,), lengths may differ) by ``max_new_tokens`` tokens each,
+    decoding them together: every decode step streams the weights once for all sequences (the multi-row GEMVs; attention runs per
+    sequence). Sequence b gets exactly the tokens ``generate`` returns for ``prompts[b]`` alone (under sampling: with
+    ``SamplerRNG(seed=seeds[b])``). Each prompt is prefilled alone into slot b of the KV cache, which is rebuilt for
+    ``len(prompts)`` sequences when it holds fewer. A sequence that meets ``eos_id`` stops collecting tokens; the
+    batch steps on until all have or ``max_new_tokens`` is reached. Returns the (T_b + new_b,) ids per sequence."""
+    B = len(prompts)
+    if B == 0:
+        raise ValueError("generate_batch: no prompts")
+    if B > MAX_BATCH:
+        raise NotImplementedError(f"generate_batch: {B} prompts; the MI355X batched decode runs at most {MAX_BATCH} "
+                                  "sequences per step")
+    if max_new_tokens < 1:
+        raise ValueError("generate_batch: max_new_tokens must be at least 1")
+    if seeds is not None and len(seeds) != B:
+        raise ValueError(f"generate_batch: {len(seeds)} seeds for {B} prompts")
+    longest = max(p.size(0) for p in prompts)
+    if model.max_seq_length < longest + max_new_tokens - 1:
+        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= "
+                                  f"{longest + max_new_tokens - 1}")
+    if B > 1 and temperature > 0.0 and not graph_sampling(model, temperature, top_k):
+        raise NotImplementedError("generate_batch: sampling a batch runs on the device sampler only (temperature > 0 "
+                                  f"with top_k in [1, {ops.MAX_TOP_K}] over bf16 logits)")
+    device = prompts[0].device
+    rngs = None
+    if temperature > 0.0:
+        rngs = [SamplerRNG(device, None if seeds is None else seeds[b]) for b in range(B)]
+    if B == 1:
+        return [generate(model, prompts[0], prompts[0].size(0) + max_new_tokens, temperature=temperature, top_k=top_k,
+                         eos_id=eos_id, use_graph=use_graph, rng=None if rngs is None else rngs[0])]
+    kv = model.transformer.h[0].attn.kv_cache
+    if kv is None or kv.k.size(0) < B:
+        model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.k.dtype)
+    firsts = []
+    for b, prompt in enumerate(prompts):  # the single path's prefill (next_token), on slot b
+        T = prompt.size(0)
+        logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=b)
+        firsts.append(sample(logits, temperature=temperature, top_k=top_k,
+                             rng=None if rngs is None else rngs[b]).to(dtype=prompt.dtype).clone())
+    n_steps = max_new_tokens - 1
+    if n_steps <= 0:
+        return [torch.cat([p, f]) for p, f in zip(prompts, firsts)]
+    from lit_gpt.runtime import BatchDecodeGraph
+
+    dg = BatchDecodeGraph(model, torch.cat(firsts), [p.size(0) for p in prompts],
+                          chunk=DECODE_CHUNK if use_graph and n_steps > DECODE_CHUNK else 1,
+                          temperature=temperature, top_k=top_k, rngs=rngs, use_graph=use_graph)
+    out, lengths = _batch_steps(dg, n_steps, eos_id)
+    return [torch.cat([p, f, out[:n_b, b].to(p.dtype)]) for b, (p, f, n_b) in enumerate(zip(prompts, firsts, lengths))]
 
 
 def _check_collectives() -> None:
@@ -273,8 +366,10 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
          top_k: Optional[int] = 200, temperature: float = 0.8,
          checkpoint_dir: Path = Path("checkpoints/stabilityai/stablelm-base-alpha-3b"),
          quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
-         synthetic: Optional[str] = None, prompt_len: int = 16) -> None:
+         synthetic: Optional[str] = None, prompt_len: int = 16, batch_size: int = 1) -> None:
     precision = precision or "bf16-true"
+    if not 1 <= batch_size <= MAX_BATCH:
+        raise NotImplementedError(f"--batch_size {batch_size}: the batched decode runs 1..{MAX_BATCH} sequences")
     if precision not in ("bf16-true", "32-true"):
         raise NotImplementedError("the MI355X path computes in bf16 (bf16-true) or fp32 (32-true)")
     dtype = torch.float32 if precision == "32-true" else torch.bfloat16
@@ -303,7 +398,22 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
     print(f"Time to load the model weights: {time.perf_counter() - t0:.02f} seconds.", file=sys.stderr)
     torch.manual_seed(1234)
     eos_id = tokenizer.eos_id if tokenizer is not None else None
-    for i in range(num_samples):
+    for i in range(0, num_samples if batch_size > 1 else 0, batch_size):
+        # --batch_size B: the samples B at a time, decoded together (generate_batch; each its own sampler seed)
+        nb = min(batch_size, num_samples - i)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys = generate_batch(model, [encoded] * nb, max_new_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        for block in model.transformer.h:
+            block.attn.kv_cache.reset_parameters()
+        for y in ys:
+            print(tokenizer.decode(y) if tokenizer is not None else y.tolist())
+        tokens_generated = sum(y.size(0) - prompt_length for y in ys)
+        print(f"Time for inference {i // batch_size + 1}: {t:.02f} sec total, {tokens_generated / t:.02f} tokens/sec",
+              file=sys.stderr)
+    for i in range(num_samples if batch_size == 1 else 0):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         y = generate(model, encoded, max_returned_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id)
@@ -331,10 +441,12 @@ def _cli(argv=None) -> None:
     p.add_argument("--compile", action="store_true")
     p.add_argument("--synthetic", default=None, help="random-init model of this registered config name")
     p.add_argument("--prompt_len", type=int, default=16)
+    p.add_argument("--batch_size", type=int, default=1,
+                   help="decode the samples this many at a time (1..4) through generate_batch")
     a = p.parse_args(argv)
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,
-         compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len)
+         compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, batch_size=a.batch_size)
 
 
 if __name__ == "__main__":

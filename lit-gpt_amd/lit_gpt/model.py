@@ -92,12 +92,18 @@ class GPT(nn.Module):
 
     def forward(self, idx: torch.Tensor, input_pos: Optional[torch.Tensor] = None, *,
                 last_token_only: bool = False, embedded: Optional[torch.Tensor] = None,
-                hidden_only: bool = False) -> torch.Tensor:
+                hidden_only: bool = False, kv_slot: int = 0) -> torch.Tensor:
         """(B=1, T) ids -> (1, T, padded_vocab) logits; ``last_token_only`` computes only the last row (1, 1, V)
         — all that ``generate`` samples from (generate/base.py:31). ``embedded`` (T * n_embd bf16) is
         ``transformer.wte(idx)`` already gathered — by the previous decode step's ``ops.argmax_embed`` in
         ``DecodeGraph`` — and replaces the embedding launch. ``hidden_only`` stops before ln_f / lm_head and returns
-        the last block's output (DecodeGraph runs the head fused with the greedy argmax)."""
+        the last block's output (DecodeGraph runs the head fused with the greedy argmax). ``kv_slot``: the slot of a
+        ``set_kv_cache(batch_size > 1)`` cache that a B = 1 call reads and writes.
+
+        (B <= MAX_BATCH = 4, T) with a KV cache is the batched form (``_forward_batch``): T > 1 runs each row as the
+        B = 1 prefill on slot b at the shared ``input_pos`` (T,); T = 1 is one batched decode step, ``input_pos`` (1,)
+        shared or (B,) / (B, 1) one position per sequence, ``embedded`` (B * n_embd). Row b has the bits of the B = 1
+        call on that sequence."""
         B, T = idx.shape
         if self.max_seq_length < T:
             raise ValueError(f"Cannot forward sequence of length {T}, max seq length is only {self.max_seq_length}.")
@@ -106,7 +112,7 @@ class GPT(nn.Module):
         if not idx.is_cuda:
             _gpu_only("GPT.forward")
         if B != 1:
-            raise NotImplementedError("the MI355X decode path runs batch size 1 (as generate/base.py does)")
+            return self._forward_batch(idx, input_pos, last_token_only, embedded, hidden_only)
         cos, sin = self._rope_tables()
         if input_pos is not None:
             input_pos = input_pos.to(device=idx.device, dtype=torch.int64).contiguous()
@@ -117,7 +123,8 @@ class GPT(nn.Module):
         else:
             x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(1, T, -1)
         for block in self.transformer.h:
-            x = block(x, cos, sin, None, input_pos)
+            x = block(x, cos, sin, None, input_pos) if kv_slot == 0 else block(x, cos, sin, None, input_pos,
+                                                                              kv_slot=kv_slot)
         if last_token_only:
             x = x[:, -1:].contiguous()
         if hidden_only:
@@ -126,6 +133,81 @@ class GPT(nn.Module):
         if isinstance(ln, RMSNorm):
             return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps)
         return _lin(self.lm_head, ln(x))
+
+    # Sequences per batched decode step. The rows kernels take up to ops.MAX_GEMV_ROWS = 8 rows, but measured on the
+    # Llama-2-7B shapes an 8-row launch is no faster than the MFMA prefill GEMM at 8 rows, while at 2
+    # and 4 rows it beats both that GEMM and M one-row launches: 4 is the largest measured batch where both hold
+    MAX_BATCH = 4
+
+    def _batch_check(self, B: int) -> None:
+        """What the batched route (B > 1) covers: up to MAX_BATCH sequences, dense RMSNorm / LLaMAMLP blocks whose
+        Linears are all 4-bit ``QuantLinear`` and carry no hooks. Everything else is refused here, before any launch."""
+        if B > self.MAX_BATCH:
+            raise NotImplementedError(f"batch size {B}: the MI355X batched decode runs at most {self.MAX_BATCH} "
+                                      "sequences per step")
+
+        def four_bit(lin, name):
+            if type(lin) is not quantize.QuantLinear or lin._forward_hooks:
+                raise NotImplementedError(
+                    f"batch size > 1 with {name} a {type(lin).__name__}: the multi-row decode GEMV streams plain "
+                    f"4-bit Linears only (--quantize {quantize.ROWS_MODES}); LoRA-attached, bnb.int8, bf16 and fp32 "
+                    "Linears decode one sequence at a time")
+
+        for i, blk in enumerate(self.transformer.h):
+            if blk.config.parallel_residual or not isinstance(blk.norm_1, RMSNorm):
+                raise NotImplementedError("batch size > 1 with parallel-residual (GPT-NeoX) blocks: the batched decode "
+                                          "runs RMSNorm / LLaMAMLP blocks only")
+            if not isinstance(blk.mlp, LLaMAMLP):
+                raise NotImplementedError(f"batch size > 1 with a {type(blk.mlp).__name__} (sparse-MoE) block: the "
+                                          "routed expert kernels decode one sequence at a time")
+            if blk.attn._forward_hooks or blk.mlp._forward_hooks or blk._forward_hooks:
+                raise NotImplementedError("batch size > 1 with forward hooks on a block (tensor parallelism): the "
+                                          "fused GEMV + all-reduce decodes one sequence at a time")
+            for name in ("attn.attn", "attn.proj", "mlp.fc_1", "mlp.fc_2", "mlp.proj"):
+                four_bit(blk.get_submodule(name), f"transformer.h.{i}.{name}")
+        four_bit(self.lm_head, "lm_head")
+        if not isinstance(self.transformer.ln_f, RMSNorm):
+            raise NotImplementedError("batch size > 1 needs an RMSNorm ln_f")
+
+    def _forward_batch(self, idx, input_pos, last_token_only, embedded, hidden_only) -> torch.Tensor:
+        """The B > 1 forms of ``forward`` (its docstring). T = 1 per block: the rows qkv GEMV with norm_1 fused, the
+        one-sequence decode attention once per sequence on its cache slot, the rows out-projection + residual, the
+        rows SwiGLU pair with norm_2 fused, the rows down-projection + residual; then ln_f fused into the rows
+        lm_head. Every launch is serial on the current stream, so the step captures as one unbranched HIP graph."""
+        B, T = idx.shape
+        self._batch_check(B)
+        if input_pos is None:
+            raise NotImplementedError("batch size > 1 runs with a KV cache only (pass input_pos)")
+        kv = self.transformer.h[0].attn.kv_cache
+        if kv is None or kv.k.size(0) < B:
+            raise ValueError(f"batch size {B} needs set_kv_cache(batch_size >= {B})")
+        input_pos = input_pos.to(device=idx.device, dtype=torch.int64)
+        if T > 1:  # the reference's shared positions: each row is the B = 1 prefill on its slot
+            if embedded is not None:
+                raise ValueError("embedded: one token per sequence (T = 1) only")
+            return torch.cat([self.forward(idx[b:b + 1], input_pos, last_token_only=last_token_only,
+                                           hidden_only=hidden_only, kv_slot=b) for b in range(B)])
+        if input_pos.numel() == 1:
+            pos = input_pos.reshape(1).expand(B).contiguous()
+        elif input_pos.numel() == B:
+            pos = input_pos.reshape(B).contiguous()
+        else:
+            raise ValueError(f"input_pos must hold 1 (shared) or {B} (one per sequence) positions for a batched "
+                             f"decode step, got shape {tuple(input_pos.shape)}")
+        cos, sin = self._rope_tables()
+        C = self.transformer.wte.weight.shape[1]
+        if embedded is not None:
+            if embedded.numel() != B * C or embedded.dtype != torch.bfloat16:
+                raise ValueError("embedded must hold B * n_embd bf16 values (the gathered wte rows of idx)")
+            x = embedded.view(B, C)
+        else:
+            x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(B, C)
+        for block in self.transformer.h:
+            x = block.decode_rows(x, cos, sin, pos)
+        if hidden_only:
+            return x.view(B, 1, C)
+        ln = self.transformer.ln_f
+        return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps, rows=True).view(B, 1, -1)
 
     @classmethod
     def from_name(cls, name: str, **kwargs: Any) -> "GPT":
@@ -160,14 +242,22 @@ class Block(nn.Module):
         self.mlp = config.mlp_class(config)
         self.config = config
 
+    def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+        """One batched decode step (GPT._forward_batch has checked the block): x (B, C), one token of each of B
+        sequences at ``pos`` (B,), on the multi-row GEMVs; row b has the bits of ``forward`` on that sequence."""
+        x = self.attn.decode_rows(x, cos, sin, pos, norm=self.norm_1, residual=x)
+        g = quantize.swiglu(self.mlp.fc_1, self.mlp.fc_2, x, self.norm_2, rows=True)
+        return _lin(self.mlp.proj, g, residual=x, rows=True)
+
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                input_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+                input_pos: Optional[torch.Tensor] = None, *, kv_slot: int = 0) -> torch.Tensor:
         c = self.config
+        slot = {"kv_slot": kv_slot} if kv_slot else {}  # (slot 0: the attention call as it always was)
         if c.shared_attention_norm and not c.parallel_residual:
             raise NotImplementedError("No checkpoint amongst the ones we support uses this configuration"
                                       " (non-parallel residual and shared attention norm).")
         if c.parallel_residual:
-            return self._parallel_forward(x, cos, sin, mask, input_pos)
+            return self._parallel_forward(x, cos, sin, mask, input_pos, **slot)
         if not isinstance(self.norm_1, RMSNorm) or not isinstance(self.mlp, (LLaMAMLP, LLaMAMoE)):
             raise NotImplementedError(f"{type(self.mlp).__name__} / {type(self.norm_1).__name__} blocks have no "
                                       "MI355X kernels in this build")
@@ -183,11 +273,11 @@ class Block(nn.Module):
         ha = comm.tp_hook(self.attn)
         hm = comm.tp_hook(self.mlp)
         if ha is not None:
-            x = self.attn.forward(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x, reduce=ha)
+            x = self.attn.forward(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x, reduce=ha, **slot)
         elif not self.attn._forward_hooks:
-            x = self.attn(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x)
+            x = self.attn(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x, **slot)
         else:
-            x = ops.add(self.attn(self.norm_1(x), cos, sin, mask, input_pos).contiguous(), x.contiguous())
+            x = ops.add(self.attn(self.norm_1(x), cos, sin, mask, input_pos, **slot).contiguous(), x.contiguous())
         if hm is not None and isinstance(self.mlp, LLaMAMLP):
             return self.mlp.forward(x, norm=self.norm_2, residual=x, reduce=hm)
         if hm is not None:
@@ -197,13 +287,13 @@ class Block(nn.Module):
         return ops.add(self.mlp(self.norm_2(x)).contiguous(), x)
 
 
-    def _parallel_forward(self, x, cos, sin, mask, input_pos) -> torch.Tensor:
+    def _parallel_forward(self, x, cos, sin, mask, input_pos, **slot) -> torch.Tensor:
         """GPT-NeoX block (reference model.py:572-593, parallel_residual): n_1 = norm_1(x), h = attn(n_1),
         n_2 = n_1 if shared_attention_norm else norm_2(x), x = mlp(n_2) + h + x — the reference's association:
         bf16(mlp + h) (fused into the mlp.proj epilogue) then + x. Under tensor parallelism the attn / mlp outputs
         go through their all-reduce hooks first (generate/tp.py), as in the reference."""
         n_1 = self.norm_1(x)
-        h = self.attn(n_1, cos, sin, mask, input_pos).contiguous()
+        h = self.attn(n_1, cos, sin, mask, input_pos, **slot).contiguous()
         n_2 = n_1 if self.config.shared_attention_norm else self.norm_2(x)
         if self.mlp._forward_hooks:  # TP: the hook must see the mlp output alone
             m = ops.add(self.mlp(n_2).contiguous(), h)
@@ -227,10 +317,11 @@ class CausalSelfAttention(nn.Module):
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor] = None,
                 input_pos: Optional[torch.Tensor] = None, *, norm: Optional["RMSNorm"] = None,
-                residual: Optional[torch.Tensor] = None, reduce=None) -> torch.Tensor:
+                residual: Optional[torch.Tensor] = None, reduce=None, kv_slot: int = 0) -> torch.Tensor:
         """``norm`` / ``residual`` / ``reduce`` are fusion hooks used by Block.forward: the RMSNorm runs in the qkv
         GEMV prologue, the residual add (and under TP the all-reduce hook ``reduce``) in the proj epilogue. Without
-        them this is the reference forward."""
+        them this is the reference forward. ``kv_slot``: the slot of a batch KV cache (``set_kv_cache(batch_size >
+        1)``) this B = 1 call reads and writes."""
         B, T, C = x.size()
         c = self.config
         H, G, hs = c.n_head, c.n_query_groups, c.head_size
@@ -249,11 +340,22 @@ class CausalSelfAttention(nn.Module):
             kv = self.kv_cache
             if kv.k.dtype != qkv.dtype:  # reference KVCache.forward casts to the activation dtype (:790-791)
                 kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
-            kc, vc = kv.k, kv.v
+            if not 0 <= kv_slot < kv.k.size(0):
+                raise ValueError(f"kv_slot {kv_slot}: the KV cache holds {kv.k.size(0)} sequence(s)")
+            kc, vc = (kv.k, kv.v) if kv.k.size(0) == 1 else (kv.k[kv_slot], kv.v[kv_slot])
             pos = input_pos
             # callers may pass the full cos/sin tables (our GPT.forward) or rows pre-selected by input_pos (the
             # reference's GPT.forward, model.py:505-506)
             rope_pos = pos if (cos.size(0) != T or T == kc.size(-2)) else torch.arange(T, device=dev)
+        y = self._attend(qkv, kc, vc, pos, rope_pos, cos, sin)
+        out = _lin(self.proj, y.view(1, T, H * hs), residual=residual, reduce=reduce)
+        return out.view(B, T, -1)
+
+    def _attend(self, qkv, kc, vc, pos, rope_pos, cos, sin, out=None) -> torch.Tensor:
+        """RoPE + KV-append + causal attention of the T rows of ``qkv`` over one sequence's caches -> (T, H * hs)."""
+        c = self.config
+        H, G, hs = c.n_head, c.n_query_groups, c.head_size
+        T, dev = qkv.size(0), qkv.device
         cos = cos.to(device=dev, dtype=torch.float32).contiguous()
         sin = sin.to(device=dev, dtype=torch.float32).contiguous()
         S = kc.size(-2)
@@ -266,13 +368,28 @@ class CausalSelfAttention(nn.Module):
                 ws = self._attn_ws = ops.AttentionWorkspace(1, H, G, hs, n_splits, dev)
         if T == 1 and self.fuse_decode and ops.decode_fusable(hs, c.rope_n_elem) and qkv.dtype == torch.bfloat16:
             # decode token: RoPE + KV-append + attention in a single launch
-            y = ops.attention_decode_fused(qkv, kc, vc, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem,
-                                           1.0 / math.sqrt(hs), n_splits, workspace=ws)
-        else:
-            q = ops.rope_kv_append(qkv, kc, vc, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem)
-            y = ops.attention(q, kc, vc, pos, H, G, hs, 1.0 / math.sqrt(hs), n_splits, workspace=ws)
-        out = _lin(self.proj, y.view(1, T, H * hs), residual=residual, reduce=reduce)
-        return out.view(B, T, -1)
+            return ops.attention_decode_fused(qkv, kc, vc, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem,
+                                              1.0 / math.sqrt(hs), n_splits, workspace=ws, out=out)
+        q = ops.rope_kv_append(qkv, kc, vc, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem)
+        return ops.attention(q, kc, vc, pos, H, G, hs, 1.0 / math.sqrt(hs), n_splits, workspace=ws, out=out)
+
+    def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, *,
+                    norm: "RMSNorm", residual: torch.Tensor) -> torch.Tensor:
+        """Batched decode step: x (B, C), one token of each of B sequences at ``pos`` (B,). The qkv and the
+        out-projection run once for all rows (multi-row GEMVs); attention cannot share anything across sequences
+        (each has its own K / V), so the one-sequence decode attention runs once per sequence on row b of qkv and
+        cache slot b, all through the one ``AttentionWorkspace`` (serial launches; its counters re-arm)."""
+        c = self.config
+        B = x.size(0)
+        kv = self.kv_cache
+        qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
+        if kv.k.dtype != qkv.dtype:
+            kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
+        y = torch.empty(B, c.n_head * c.head_size, dtype=qkv.dtype, device=qkv.device)
+        for b in range(B):
+            p = pos[b:b + 1]
+            self._attend(qkv[b:b + 1], kv.k[b], kv.v[b], p, p, cos, sin, out=y[b:b + 1])
+        return _lin(self.proj, y, residual=residual, rows=True)
 
     def scaled_dot_product_attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                      mask: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -44,6 +44,8 @@ SIGNATURES = {
     "lga_nf4_double_quant": [_P, _L, _P, _P, _P],
     "lga_q4_gemv": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
     "lga_q4_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
+    "lga_q4_gemv_rows": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
+    "lga_q4_gemv_swiglu_rows": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P],
     "lga_q4_gemm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "lga_q4f_fits": [_I, _I, _I, _I, _I],
     "lga_q4f_workspace_bytes": [_I, _I, _I, _I],
@@ -217,6 +219,59 @@ def q4_gemv_swiglu(x, qw1, sc1, qw2, sc2, N, K, group, fmt, *, norm_weight=None,
                                              _dev(sc1, "sc1"), _dev(qw2, "qw2", torch.uint8), _dev(sc2, "sc2"),
                                              _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
                                              _dev(y, "y", torch.bfloat16), N, K, group, fmt, variant, _stream()))
+    return y
+
+
+MAX_GEMV_ROWS = 8  # rows of one lga_q4_gemv*_rows launch == sequences of one batched decode step
+
+
+def _gemv_rows(x, K, name):
+    """The row count M of a (M, K) activation block for the rows GEMVs (1..MAX_GEMV_ROWS)."""
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"{name}: x must be (M, K={K}), got {tuple(x.shape)}")
+    M = x.shape[0]
+    if not 1 <= M <= MAX_GEMV_ROWS:
+        raise ValueError(f"{name}: M must be 1..{MAX_GEMV_ROWS} rows, got {M}")
+    return M
+
+
+def _rows_out(out, M, N, x, name):
+    if out is None:
+        return torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    if tuple(out.shape) != (M, N):
+        raise ValueError(f"{name}: out must be ({M}, {N}), got {tuple(out.shape)}")
+    return out
+
+
+def q4_gemv_rows(x, qweight, scales, N, K, group, fmt, *, bias=None, residual=None, norm_weight=None, eps=1e-5,
+                 out=None):
+    """Y (M, N) = X (M, K) . dequant(W)^T [+bias] [+residual (M, N)] for 1 <= M <= 8 rows in one pass over the
+    weights; row r has the bits of ``q4_gemv(x[r], ..., residual=residual[r], variant=-1)``."""
+    M = _gemv_rows(x, K, "q4_gemv_rows")
+    if fmt not in (FMT_Q4G, FMT_NF4, FMT_FP4):
+        raise ValueError(f"q4_gemv_rows: fmt must be 0 (int4-g), 1 (nf4) or 3 (fp4), got {fmt}")
+    if residual is not None and tuple(residual.shape) != (M, N):
+        raise ValueError(f"q4_gemv_rows: residual must be ({M}, {N}), got {tuple(residual.shape)}")
+    y = _rows_out(out, M, N, x, "q4_gemv_rows")
+    _check(load_library().lga_q4_gemv_rows(_dev(x, "x", torch.bfloat16), _dev(qweight, "qweight", torch.uint8),
+                                           _dev(scales, "scales"), _opt(bias, "bias", torch.bfloat16),
+                                           _opt(residual, "residual", torch.bfloat16),
+                                           _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                           _dev(y, "y", torch.bfloat16), M, N, K, group, fmt, _stream()))
+    return y
+
+
+def q4_gemv_swiglu_rows(x, qw1, sc1, qw2, sc2, N, K, group, fmt, *, norm_weight=None, eps=1e-5, out=None):
+    """Y (M, N) = bf16(silu(bf16(X W1^T))) * bf16(X W2^T) for 1 <= M <= 8 rows in one pass over both weights; row r
+    has the bits of ``q4_gemv_swiglu(x[r], ..., variant=-1)``."""
+    M = _gemv_rows(x, K, "q4_gemv_swiglu_rows")
+    if fmt not in (FMT_Q4G, FMT_NF4, FMT_FP4):
+        raise ValueError(f"q4_gemv_swiglu_rows: fmt must be 0 (int4-g), 1 (nf4) or 3 (fp4), got {fmt}")
+    y = _rows_out(out, M, N, x, "q4_gemv_swiglu_rows")
+    _check(load_library().lga_q4_gemv_swiglu_rows(_dev(x, "x", torch.bfloat16), _dev(qw1, "qw1", torch.uint8),
+                                                  _dev(sc1, "sc1"), _dev(qw2, "qw2", torch.uint8), _dev(sc2, "sc2"),
+                                                  _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                                  _dev(y, "y", torch.bfloat16), M, N, K, group, fmt, _stream()))
     return y
 
 

@@ -69,6 +69,10 @@ _MODES = {
 }
 
 
+# the --quantize modes whose Linears the batched decode route (B > 1) runs
+ROWS_MODES = "int4-g128/64/32, nf4, bnb.nf4, bnb.nf4-dq, bnb.fp4, bnb.fp4-dq"
+
+
 def parse_mode(mode: str):
     if mode not in _MODES:
         raise NotImplementedError(
@@ -94,9 +98,13 @@ class _Kernels:
     kind = property(lambda self: type(self).__name__)  # the Linear's name in error messages
 
     def forward(self, x: torch.Tensor, *, residual: Optional[torch.Tensor] = None,
-                norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5) -> torch.Tensor:
+                norm_weight: Optional[torch.Tensor] = None, norm_eps: float = 1e-5, rows: bool = False) -> torch.Tensor:
         """y = linear(x) [+ residual], x RMSNorm-ed first when ``norm_weight`` is given: in the one-row launch's
-        prologue where it takes the norm, else as a separate ``lga_rmsnorm``."""
+        prologue where it takes the norm, else as a separate ``lga_rmsnorm``. ``rows``: the batched decode route
+        (GPT.forward with B > 1, T = 1) — the x rows are one token each of the batch's sequences (at most 8 rows) and
+        go through ``gemv_rows``, whose row r has the bits ``gemv`` gives for x[r]; nothing else sets it."""
+        if rows:
+            return self._forward_rows(x, residual, norm_weight, norm_eps)
         lead = x.shape[:-1]
         x2 = x.reshape(-1, self.in_features)
         if x2.dtype != self.act_dtype:
@@ -112,6 +120,25 @@ class _Kernels:
     def gemv_fuses_norm(self, dual: bool = False) -> bool:
         """Whether the one-row launch (``dual``: the SwiGLU pair's) takes the RMSNorm of a row of this K."""
         return True
+
+    def _forward_rows(self, x, residual, norm_weight, norm_eps) -> torch.Tensor:
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, self.in_features)
+        if x2.dtype != self.act_dtype:
+            raise TypeError(f"{self.kind} expects {self.expects}, got {x2.dtype}")
+        x2 = x2.contiguous()
+        res = None if residual is None else residual.reshape(x2.shape[0], self.out_features).contiguous()
+        if norm_weight is not None and not self.gemv_fuses_norm():
+            x2, norm_weight = ops.rmsnorm(x2, norm_weight, norm_eps), None
+        return self.gemv_rows(x2, res, norm_weight, norm_eps).view(*lead, self.out_features)
+
+    def gemv_rows(self, x, res, norm_weight, eps):
+        """Up to 8 rows in one pass over the weights (batched decode): the 4-bit formats have the kernel."""
+        raise NotImplementedError(f"batched decode (batch size > 1) with a {self.kind}: the multi-row decode GEMV "
+                                  f"streams 4-bit weights only ({ROWS_MODES})")
+
+    def gemv_swiglu_rows(self, o, x, norm_weight, eps):
+        return self.gemv_rows(x, None, norm_weight, eps)  # (raises: only QuantLinear overrides the pair)
 
     def pairs_with(self, o: "_Kernels") -> bool:
         """Whether ``self`` and ``o`` (fc_1, fc_2) can share one dual launch: here what every format asks."""
@@ -177,6 +204,14 @@ class QuantLinear(_Kernels, nn.Module):
     def gemv(self, x, res, norm_weight, eps):
         return ops.q4_gemv(x, self.qweight, self.scales, self.out_features, self.in_features, self.group, self.fmt,
                            bias=self.bias, residual=res, norm_weight=norm_weight, eps=eps, variant=self.gemv_variant)
+
+    def gemv_rows(self, x, res, norm_weight, eps):
+        return ops.q4_gemv_rows(x, self.qweight, self.scales, self.out_features, self.in_features, self.group,
+                                self.fmt, bias=self.bias, residual=res, norm_weight=norm_weight, eps=eps)
+
+    def gemv_swiglu_rows(self, o, x, norm_weight, eps):
+        return ops.q4_gemv_swiglu_rows(x, self.qweight, self.scales, o.qweight, o.scales, self.out_features,
+                                       self.in_features, self.group, self.fmt, norm_weight=norm_weight, eps=eps)
 
     def gemm(self, x, res):
         N, K = self.out_features, self.in_features
@@ -335,13 +370,23 @@ def kernels(lin: nn.Module) -> _Kernels:
         "flag)")
 
 
-def swiglu(fc_1: nn.Module, fc_2: nn.Module, x: torch.Tensor, norm: Optional[nn.Module] = None) -> torch.Tensor:
+def swiglu(fc_1: nn.Module, fc_2: nn.Module, x: torch.Tensor, norm: Optional[nn.Module] = None, *,
+           rows: bool = False) -> torch.Tensor:
     """bf16(silu(fc_1 n)) * fc_2 n for n = norm(x) (an RMSNorm; x itself without one), x (M, K) contiguous: one
     dual GEMV launch for one row and one fused GEMM launch for several where the pair is eligible and the format
-    has the kernel, else the two Linears and ``lga_swiglu``. The norm runs once for the pair."""
+    has the kernel, else the two Linears and ``lga_swiglu``. The norm runs once for the pair. ``rows`` (batched
+    decode, M <= 8 rows): the dual rows GEMV, row r with the bits of the one-row launch on x[r]."""
     f1, f2 = kernels(fc_1), kernels(fc_2)
     norm_weight, norm_eps = (None, 1e-5) if norm is None else (norm.weight, norm.eps)
     M, pair = x.shape[0], f1.pairs_with(f2)
+    if rows:
+        if pair:
+            if norm_weight is not None and not f1.gemv_fuses_norm(dual=True):
+                x, norm_weight = ops.rmsnorm(x, norm_weight, norm_eps), None
+            return f1.gemv_swiglu_rows(f2, x, norm_weight, norm_eps)
+        # as the one-row path of an unpaired fc_1 / fc_2 (biases): the norm once, two Linears, lga_swiglu
+        n = x if norm_weight is None else ops.rmsnorm(x, norm_weight, norm_eps)
+        return ops.swiglu(f1(n, rows=True).contiguous(), f2(n, rows=True).contiguous())
     if M == 1 and pair:
         if norm_weight is not None and not f1.gemv_fuses_norm(dual=True):
             x, norm_weight = ops.rmsnorm(x, norm_weight, norm_eps), None

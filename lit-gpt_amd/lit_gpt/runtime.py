@@ -104,3 +104,78 @@ class DecodeGraph:
             raise RuntimeError("DecodeGraph was built with chunk=1")
         self.chunk_graph.replay()
         return self.history
+
+
+class BatchDecodeGraph:
+    """``DecodeGraph`` for B <= GPT.MAX_BATCH (4) sequences that decode in lock step (generate.base.generate_batch):
+    one graph per step over device-resident ``token`` (B,), ``pos`` (B,) and ``x_emb`` (B, C). The step is the batched forward
+    (GPT._forward_batch: every weight streamed once for all B rows), then per sequence the same head bookkeeping as
+    the single path — ``ops.argmax_embed`` (or ``ops.sample_topk`` with that sequence's RNG) on row b of the logits,
+    writing ``token[b]``, advancing ``pos[b]`` and gathering ``x_emb[b]``. Every launch is on one stream, so the
+    captured graph is a chain without branches; a step has no host synchronisation. ``chunk`` > 1 also captures
+    ``chunk`` steps as one graph whose tokens land in ``history`` (chunk, B)."""
+
+    def __init__(self, model, first_tokens: torch.Tensor, first_pos, chunk: int = 1, *, temperature: float = 0.0,
+                 top_k: Optional[int] = None, rngs=None, use_graph: bool = True) -> None:
+        """``first_tokens`` (B,): each sequence's newest token; ``first_pos``: its position per sequence. Runs one
+        real step eagerly, then captures. ``use_graph=False`` keeps every step eager (tests A/B the two)."""
+        dev = first_tokens.device
+        B = first_tokens.numel()
+        self.model, self.B = model, B
+        self.temperature, self.top_k, self.rngs = float(temperature), top_k, rngs
+        if self.temperature > 0.0 and (rngs is None or len(rngs) != B or top_k is None
+                                       or not 1 <= top_k <= ops.MAX_TOP_K):
+            raise ValueError("BatchDecodeGraph: sampling needs top_k in [1, 1024] and one rng per sequence")
+        wte = model.transformer.wte.weight
+        if not (wte.is_cuda and wte.dtype == torch.bfloat16 and wte.is_contiguous() and wte.shape[1] % 8 == 0):
+            raise NotImplementedError("batched decode needs a contiguous bf16 embedding table with n_embd % 8 == 0")
+        self.token = first_tokens.reshape(B).to(torch.int32).clone()
+        self.pos = torch.as_tensor(first_pos, dtype=torch.int64, device=dev).reshape(B).clone()
+        self.x_emb = torch.empty(B, wte.shape[1], dtype=torch.bfloat16, device=dev)
+        self.chunk = max(1, int(chunk))
+        self.history = torch.zeros(self.chunk, B, dtype=torch.int64, device=dev)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.chunk_graph: Optional[torch.cuda.CUDAGraph] = None
+        self._step_body(embedded=False)  # embeds first_tokens itself; its head calls leave x_emb for the graphs
+        if not use_graph:
+            return
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._step_body()
+        self.graph = g
+        if self.chunk > 1:
+            gc = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gc):
+                for i in range(self.chunk):
+                    self._step_body(self.history[i])
+            self.chunk_graph = gc
+
+    def _step_body(self, idx_out: Optional[torch.Tensor] = None, embedded: bool = True) -> None:
+        model, B = self.model, self.B
+        logits = model(self.token.view(B, 1), self.pos, embedded=self.x_emb if embedded else None).view(B, -1)
+        table = model.transformer.wte.weight
+        for b in range(B):
+            out = None if idx_out is None else idx_out[b:b + 1]
+            if self.temperature > 0.0:
+                ops.sample_topk(logits[b], self.top_k, self.temperature, seed=self.rngs[b].seed,
+                                counter=self.rngs[b].counter, out_idx=out, token_out=self.token[b:b + 1],
+                                pos_inout=self.pos[b:b + 1], table=table, emb_out=self.x_emb[b])
+            else:
+                ops.argmax_embed(logits[b], table, self.x_emb[b], out_idx=out, token_out=self.token[b:b + 1],
+                                 pos_inout=self.pos[b:b + 1])
+
+    def step(self) -> torch.Tensor:
+        """One decode step of all B sequences; returns the (device, int32) buffer of their new tokens."""
+        if self.graph is None:
+            self._step_body()
+        else:
+            self.graph.replay()
+        return self.token
+
+    def steps(self) -> torch.Tensor:
+        """``chunk`` decode steps in one graph launch; returns the (device, int64) (chunk, B) buffer of tokens."""
+        if self.chunk_graph is None:
+            raise RuntimeError("BatchDecodeGraph was built with chunk=1 or without graphs")
+        self.chunk_graph.replay()
+        return self.history
