@@ -213,6 +213,24 @@ int lga_attention_decode_fused(const void* qkv, void* k_cache, void* v_cache, co
                                const int64_t* rope_pos, const float* cos, const float* sin, int rope_rows, void* y,
                                float* workspace, unsigned* counters, int n_head, int n_query_groups, int head_size,
                                int rope_n_elem, int max_seq, int n_splits, float scale, lga_stream_t stream);
+/* Speculative verify window: the decode step above for M (1..8) rows of ONE sequence at consecutive positions. qkv is
+ * (M, (H + 2G) * hs), the rows qkv GEMV's output; row r sits at pos0[0] + r (cache and rope position, read on the
+ * device: a captured graph stays valid as the position advances). After the call y (M, H*hs), k_cache and v_cache are
+ * bit-identical to M successive lga_attention_decode_fused calls on rows 0..M-1 at those positions with the same
+ * n_splits: every workgroup is the one-row kernel's workgroup of its row (own split boundaries, own key scored last
+ * from registers); the roped k / v of all M rows are appended first, in a launch of their own. A row whose position
+ * is >= max_seq stores nothing and its y is unspecified. workspace / counters as lga_attention's, sized for T = M.
+ * Requires head_size == rope_n_elem == 128 and H/G in {1, 2, 4, 8}. */
+int lga_attention_decode_window(const void* qkv, void* k_cache, void* v_cache, const int64_t* pos0, const float* cos,
+                                const float* sin, int rope_rows, void* y, float* workspace, unsigned* counters, int M,
+                                int n_head, int n_query_groups, int head_size, int rope_n_elem, int max_seq,
+                                int n_splits, float scale, lga_stream_t stream);
+/* Greedy speculative acceptance after the window's lm_head: logits (M, n) bf16 contiguous, window (M) int32
+ * (window[0] the last emitted token, window[1..] the drafts). t_r = argmax of row r in lga_argmax's order; a = the
+ * largest a <= M - 1 with window[r + 1] == t_r for all r < a. out (M + 1) int32: out[0] = a, out[1..a+1] = t_0..t_a,
+ * the rest -1. *token_inout = t_a (may be &window[0]), *pos_inout += a + 1 (either may be NULL). 1 <= M <= 8. */
+int lga_spec_accept(const void* logits, int M, int n, const int32_t* window, int32_t* out, int32_t* token_inout,
+                    int64_t* pos_inout, lga_stream_t stream);
 
 /* -- sparse MoE (LLaMAMoE.forward, lit_gpt/model.py:727-743; Mixtral) ------------------------------------------
  * lga_moe_route: per token row of router logits [T][n_expert] bf16 -> expert_ids [T][k] int32 and probs [T][k]

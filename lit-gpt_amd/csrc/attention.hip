@@ -45,7 +45,10 @@ constexpr int kCounterStride = 64;
 
 // K/V rows are streamed once per step (the next step's re-read comes after ~1 GB of other traffic): nt loads
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+// (NT = false, the window kernel: the M rows of a verify window read the same K/V, so all but one read is a re-read)
+template <bool NT = true>
 __device__ __forceinline__ uint4 ld_kv(const uint16_t* p) {
+  if constexpr (!NT) return *(const uint4*)p;
   const u32x4_t v = __builtin_nontemporal_load((const u32x4_t*)p);
   return make_uint4(v.x, v.y, v.z, v.w);
 }
@@ -57,8 +60,18 @@ __device__ __forceinline__ uint4 ld_kv(const uint16_t* p) {
 #ifndef LGA_ATTN_SOLO
 #define LGA_ATTN_SOLO 1  // lab A/B: 0 = the workgroup-barrier publish for every slice width
 #endif
+// WINDOW (speculative verify, lga_attention_decode_window): FUSED for M rows of ONE sequence at consecutive positions;
+// grid.z = row r, whose position (cache and rope) is input_pos[0] + r and whose qkv row is row r of q. Every
+// workgroup is the T = 1 FUSED workgroup of its row — the row's own split boundaries, its own key scored last from
+// registers by row group 0 of the owning split, the same merges and combine — so y[r] has the bits of the one-row
+// launch at that position. The one difference: the roped k / v of ALL M rows are appended by window_append_kernel
+// in a launch of its own BEFORE this one (row r reads the keys of rows 0..r-1 from the cache, and other workgroups
+// of this launch own those positions: no store here may be depended on), so the owning workgroup does not store.
+#ifndef LGA_ATTN_WIN_NT
+#define LGA_ATTN_WIN_NT 0  // lab A/B: 1 = the one-row kernel's nt loads in the window kernel too
+#endif
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE>
+template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE, bool WINDOW = false>
 __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc,
                                           uint16_t* __restrict__ vc, const int64_t* __restrict__ input_pos,
                                           uint16_t* __restrict__ y, float* __restrict__ ws,
@@ -79,8 +92,10 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   const int sub = lane % LPR;
   LGA_TRACE(0);
   // both positions in one scalar round trip (hipcc otherwise waits for input_pos before issuing rope_pos)
-  const long p = input_pos[t];
-  const long rp_raw = FUSED ? rope_pos[t] : 0;
+  static_assert(!WINDOW || FUSED, "the window form is the fused form per row");
+  const long p = WINDOW ? input_pos[0] + t : input_pos[t];
+  const long rp_raw = WINDOW ? p : (FUSED ? rope_pos[t] : 0);
+  if (WINDOW) q += (size_t)t * (n_head + 2 * (gridDim.y / hsplit)) * HS;  // row t of the (M, (H + 2G) hs) qkv
   const int L = (int)min(p + 1, (long)max_seq);  // keys 0..p (never past the cache)
   const int chunk = (L + n_splits - 1) / n_splits;
   const int k_lo = split * chunk;
@@ -102,8 +117,8 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int j = max(min(j0 + u * RG, k_end - 1), 0);
-      kv[u] = ld_kv(kbase + (size_t)j * HS);
-      vv[u] = ld_kv(vbase + (size_t)j * HS);
+      kv[u] = ld_kv<!WINDOW || LGA_ATTN_WIN_NT>(kbase + (size_t)j * HS);
+      vv[u] = ld_kv<!WINDOW || LGA_ATTN_WIN_NT>(vbase + (size_t)j * HS);
     }
   };
   const int j_first = k_lo + rg;
@@ -215,7 +230,7 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
     const uint16_t* kvrow = q + ((size_t)g * (QPKT + 2) + QPKT) * HS + sub * 8;
     const uint4 kr = rope8(*(const uint4*)kvrow, cs, sn, sub);
     const uint4 vr = *(const uint4*)(kvrow + HS);
-    if (hsi == 0) {  // one head slice appends; the others score the same key from their registers
+    if (!WINDOW && hsi == 0) {  // one head slice appends; the others score the same key from their registers
       *(uint4*)(kc + ((size_t)g * max_seq + p) * HS + sub * 8) = kr;
       *(uint4*)(vc + ((size_t)g * max_seq + p) * HS + sub * 8) = vr;
     }
@@ -367,15 +382,44 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   LGA_TRACE(6);
 }
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE>
+template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE, bool WINDOW = false>
 __global__ void __launch_bounds__(NW * 64) attn_kernel(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc,
                                                    uint16_t* __restrict__ vc, const int64_t* __restrict__ input_pos,
                                                    uint16_t* __restrict__ y, float* __restrict__ ws,
                                                    unsigned* __restrict__ cnt, int n_head, int max_seq, float scale,
                                                    const int64_t* __restrict__ rope_pos, const float* __restrict__ cos,
                                                    const float* __restrict__ sin, int rope_rows, int hsplit) {
-  attn_body<HS, QPK, UNR, NW, FUSED, PIPE>(q, kc, vc, input_pos, y, ws, cnt, n_head, max_seq, scale, rope_pos, cos,
-                                           sin, rope_rows, hsplit);
+  attn_body<HS, QPK, UNR, NW, FUSED, PIPE, WINDOW>(q, kc, vc, input_pos, y, ws, cnt, n_head, max_seq, scale, rope_pos,
+                                                   cos, sin, rope_rows, hsplit);
+}
+
+// The window's KV-append: roped k and v of row r into cache row pos0[0] + r of every group, with the fused kernel's
+// own rope8 on the same operands (the same bits it stores at T = 1). Grid (G, M), one wave: lanes 0..HS/8-1 move k,
+// the next HS/8 move v. A row at or past max_seq stores nothing.
+template <int HS>
+__global__ void __launch_bounds__(64) window_append_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ kc,
+                                                          uint16_t* __restrict__ vc, const int64_t* __restrict__ pos0,
+                                                          const float* __restrict__ cos, const float* __restrict__ sin,
+                                                          int rope_rows, int n_head, int max_seq) {
+  constexpr int LPR = HS / 8;
+  const int g = blockIdx.x, G = gridDim.x, r = blockIdx.y, qpk = n_head / G;
+  const int lane = threadIdx.x, sub = lane % LPR;
+  const long p = pos0[0] + r;
+  if (lane >= 2 * LPR || p < 0 || p >= max_seq) return;
+  const uint16_t* kvrow = qkv + ((size_t)r * (n_head + 2 * G) + (size_t)g * (qpk + 2) + qpk) * HS + sub * 8;
+  const size_t dst = ((size_t)g * max_seq + p) * HS + sub * 8;
+  if (lane < LPR) {
+    const long rp = min(max(p, 0L), (long)rope_rows - 1);
+    float cs[8], sn[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      cs[i] = cos[(size_t)rp * HS + sub * 8 + i];
+      sn[i] = sin[(size_t)rp * HS + sub * 8 + i];
+    }
+    *(uint4*)(kc + dst) = rope8(*(const uint4*)kvrow, cs, sn, sub);
+  } else {
+    *(uint4*)(vc + dst) = *(const uint4*)(kvrow + HS);
+  }
 }
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -930,11 +974,11 @@ __global__ void __launch_bounds__(512, 1) attn_prefill_pair_kernel(const uint16_
 #define LGA_ATTN_Q8 2, 4
 #endif
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED>
+template <int HS, int QPK, int UNR, int NW, bool FUSED, bool WINDOW = false>
 static void launch_one(dim3 grid, hipStream_t stream, const void* q, void* kc, void* vc, const int64_t* pos, void* y,
                        float* ws, unsigned* cnt, int H, int max_seq, float scale, const int64_t* rope_pos,
                        const float* cos, const float* sin, int rope_rows, int hsplit) {
-  attn_kernel<HS, QPK, UNR, NW, FUSED, LGA_ATTN_PIPE != 0><<<grid, NW * 64, 0, stream>>>((const uint16_t*)q, (uint16_t*)kc, (uint16_t*)vc,
+  attn_kernel<HS, QPK, UNR, NW, FUSED, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>((const uint16_t*)q, (uint16_t*)kc, (uint16_t*)vc,
                                                                      pos, (uint16_t*)y, ws, cnt, H, max_seq, scale,
                                                                      rope_pos, cos, sin, rope_rows, hsplit);
 }
@@ -954,14 +998,14 @@ static int attn_hsplit(int T, int G, int qpk, int n_splits) {
   return h;
 }
 
-template <int HS, bool FUSED>
+template <int HS, bool FUSED, bool WINDOW = false>
 static int launch_hs(const void* q, void* kc, void* vc, const int64_t* pos, void* y, float* ws, unsigned* cnt, int T,
                      int H, int G, int max_seq, int n_splits, float scale, const int64_t* rope_pos, const float* cos,
                      const float* sin, int rope_rows, hipStream_t stream) {
-  const int hsplit = attn_hsplit(T, G, H / G, n_splits);
+  const int hsplit = attn_hsplit(WINDOW ? 1 : T, G, H / G, n_splits);  // a window row: the slices of its T = 1 launch
   const dim3 grid(n_splits, G * hsplit, T);
 #define LGA_ATTN(QPK, CFG)                                                                                        \
-  launch_one<HS, QPK, CFG, FUSED>(grid, stream, q, kc, vc, pos, y, ws, cnt, H, max_seq, scale, rope_pos, cos, sin, \
+  launch_one<HS, QPK, CFG, FUSED, WINDOW>(grid, stream, q, kc, vc, pos, y, ws, cnt, H, max_seq, scale, rope_pos, cos, sin, \
                                   rope_rows, hsplit)
   switch (H / G / hsplit) {
     case 1:  // one head per group: 8 waves x 2 keys in flight when the groups are few (TP ranks: G = 4 7.9 vs 8.2 us,
@@ -1057,6 +1101,37 @@ extern "C" int lga_attention_decode_fused(const void* qkv, void* k_cache, void* 
   const int rc = lga::launch_hs<128, true>(qkv, k_cache, v_cache, cache_pos, y, workspace, counters, 1, n_head,
                                            n_query_groups, max_seq, n_splits, scale, rope_pos, cos, sin, rope_rows,
                                            stream);
+  if (rc) return rc;
+  LGA_LAUNCH_RETURN();
+}
+
+// Speculative verify window: M rows of ONE sequence at consecutive positions pos0[0] + r (cache and rope position, read
+// on the device). y[r] and the caches end with the bits of M successive lga_attention_decode_fused calls with the
+// same n_splits. Two launches on the stream: the append of all M rows, then the M-row attention.
+extern "C" int lga_attention_decode_window(const void* qkv, void* k_cache, void* v_cache, const int64_t* pos0,
+                                           const float* cos, const float* sin, int rope_rows, void* y,
+                                           float* workspace, unsigned* counters, int M, int n_head,
+                                           int n_query_groups, int head_size, int rope_n_elem, int max_seq,
+                                           int n_splits, float scale, hipStream_t stream) {
+  LGA_CHECK_ARG(qkv && k_cache && v_cache && pos0 && cos && sin && y, "lga_attention_decode_window: null pointer");
+  LGA_CHECK_ARG(M >= 1 && M <= 8, "lga_attention_decode_window: M must be in [1, 8]");
+  LGA_CHECK_ARG(n_query_groups > 0 && n_head % n_query_groups == 0, "lga_attention_decode_window: bad head geometry");
+  LGA_CHECK_ARG(head_size == 128 && rope_n_elem == 128,
+                "lga_attention_decode_window: needs head_size == rope_n_elem == 128");
+  {
+    const int qpk = n_head / n_query_groups;
+    LGA_CHECK_ARG(qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8,
+                  "lga_attention_decode_window: q_per_kv must be 1, 2, 4 or 8");
+  }
+  LGA_CHECK_ARG(rope_rows > 0 && max_seq > 0, "lga_attention_decode_window: empty rope cache or kv cache");
+  LGA_CHECK_ARG(n_splits >= 1 && n_splits <= 256, "lga_attention_decode_window: n_splits must be in [1, 256]");
+  LGA_CHECK_ARG(n_splits == 1 || (workspace && counters),
+                "lga_attention_decode_window: split attention needs workspace + counters");
+  lga::window_append_kernel<128><<<dim3(n_query_groups, M), 64, 0, stream>>>(
+      (const uint16_t*)qkv, (uint16_t*)k_cache, (uint16_t*)v_cache, pos0, cos, sin, rope_rows, n_head, max_seq);
+  const int rc = lga::launch_hs<128, true, true>(qkv, k_cache, v_cache, pos0, y, workspace, counters, M, n_head,
+                                                 n_query_groups, max_seq, n_splits, scale, pos0, cos, sin, rope_rows,
+                                                 stream);
   if (rc) return rc;
   LGA_LAUNCH_RETURN();
 }

@@ -126,6 +126,85 @@ __global__ void __launch_bounds__(1024) argmax_f32_kernel(const float* __restric
   }
 }
 
+// ---- greedy speculative decoding: the verify window's argmaxes and the accepted prefix, one launch ---------------
+// logits (M, n) bf16 are the target model's rows for the window tokens window[0..M-1] (window[0] the last emitted
+// token, window[1..] the drafts). t_r = argmax of row r in argmax_kernel's order (NaN first, ties to the lowest
+// index); a = the largest a <= M - 1 with window[r + 1] == t_r for every r < a. out[0] = a, out[1..a+1] = t_0..t_a
+// (the tokens this round emits; out[a+2..M] = -1), *token_inout = t_a, *pos_inout += a + 1. One workgroup walks the
+// rows (each row is argmax_kernel's scan); M = 1 is a plain argmax step.
+constexpr int kMaxWindow = 8;
+
+template <bool VEC>
+__global__ void __launch_bounds__(1024) spec_accept_kernel(const uint16_t* __restrict__ logits, int M, int n,
+                                                           const int32_t* window, int32_t* __restrict__ out,
+                                                           int32_t* token_inout,  // (may be &window[0])
+                                                           int64_t* __restrict__ pos_inout) {
+  __shared__ float sv[kMaxWindow][16];
+  __shared__ int si[kMaxWindow][16];
+  const int wave = threadIdx.x >> 6;
+  const int64_t p0 = (pos_inout && threadIdx.x == 0) ? *pos_inout : 0;
+  for (int r = 0; r < M; ++r) {
+    const uint16_t* row = logits + (size_t)r * n;
+    float bv = -INFINITY;
+    int bi = 0x7FFFFFFF;
+    int done = 0;
+    if (VEC) {
+      const int nvec = n / 8;
+      const uint4* lv = (const uint4*)row;
+      for (int base = 0; base < nvec; base += 1024 * kVec) {
+        uint4 q[kVec];
+#pragma unroll
+        for (int u = 0; u < kVec; ++u) q[u] = lv[min(base + u * 1024 + (int)threadIdx.x, nvec - 1)];
+#pragma unroll
+        for (int u = 0; u < kVec; ++u) {
+          const int vi = base + u * 1024 + threadIdx.x;
+          const uint32_t d[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (vi < nvec) {
+              take(bflo(d[e]), vi * 8 + 2 * e, bv, bi);
+              take(bfhi(d[e]), vi * 8 + 2 * e + 1, bv, bi);
+            }
+          }
+        }
+      }
+      done = nvec * 8;
+    }
+    for (int i = done + threadIdx.x; i < n; i += blockDim.x) take(bf2f(row[i]), i, bv, bi);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(bv, off);
+      const int oi = __shfl_xor(bi, off);
+      take(ov, oi, bv, bi);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      sv[r][wave] = bv;
+      si[r][wave] = bi;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int nw = blockDim.x >> 6;
+    int a = -1, last = 0;  // a: the accepted count once a row's token differs from its draft (or the rows run out)
+    for (int r = 0; r < M; ++r) {
+      float bv = sv[r][0];
+      int bi = si[r][0];
+      for (int w = 1; w < nw; ++w) take(sv[r][w], si[r][w], bv, bi);
+      if (bi >= n) bi = 0;
+      if (a < 0) {
+        out[1 + r] = bi;
+        last = bi;
+        if (r == M - 1 || window[r + 1] != bi) a = r;  // (token_inout may be window[0]: written after the walk)
+      } else {
+        out[1 + r] = -1;
+      }
+    }
+    out[0] = a;
+    if (token_inout) *token_inout = last;
+    if (pos_inout) *pos_inout = p0 + a + 1;
+  }
+}
+
 // ---- temperature > 0: top-k + softmax + multinomial on the device (generate/base.py:30-41) -----------------------
 // The reference's default invocation (generate/base.py:102-103: top_k 200, temperature 0.8) as ONE launch inside the
 // decode graph:
@@ -451,6 +530,19 @@ extern "C" int lga_argmax_embed(const void* logits, int n, int64_t* out_idx, int
   else
     lga::argmax_kernel<false, true><<<1, 1024, 0, stream>>>((const uint16_t*)logits, n, out_idx, token_out, pos_inout,
                                                             (const uint16_t*)table, n_embd, vocab, (uint16_t*)emb_out);
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_spec_accept(const void* logits, int M, int n, const int32_t* window, int32_t* out,
+                               int32_t* token_inout, int64_t* pos_inout, hipStream_t stream) {
+  LGA_CHECK_ARG(logits && window && out && n > 0, "lga_spec_accept: bad arguments");
+  LGA_CHECK_ARG(M >= 1 && M <= lga::kMaxWindow, "lga_spec_accept: M must be in [1, 8]");
+  if (((uintptr_t)logits & 15) == 0 && n % 8 == 0)  // every row 16-B aligned
+    lga::spec_accept_kernel<true><<<1, 1024, 0, stream>>>((const uint16_t*)logits, M, n, window, out, token_inout,
+                                                          pos_inout);
+  else
+    lga::spec_accept_kernel<false><<<1, 1024, 0, stream>>>((const uint16_t*)logits, M, n, window, out, token_inout,
+                                                           pos_inout);
   LGA_LAUNCH_RETURN();
 }
 

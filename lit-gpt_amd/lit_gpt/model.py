@@ -145,29 +145,79 @@ class GPT(nn.Module):
         if B > self.MAX_BATCH:
             raise NotImplementedError(f"batch size {B}: the MI355X batched decode runs at most {self.MAX_BATCH} "
                                       "sequences per step")
+        self._rows_check("batch size > 1")
+
+    def _rows_check(self, what: str) -> None:
+        """What every multi-row decode step (the batched step, the speculative verify window) needs of the model."""
 
         def four_bit(lin, name):
             if type(lin) is not quantize.QuantLinear or lin._forward_hooks:
                 raise NotImplementedError(
-                    f"batch size > 1 with {name} a {type(lin).__name__}: the multi-row decode GEMV streams plain "
+                    f"{what} with {name} a {type(lin).__name__}: the multi-row decode GEMV streams plain "
                     f"4-bit Linears only (--quantize {quantize.ROWS_MODES}); LoRA-attached, bnb.int8, bf16 and fp32 "
                     "Linears decode one sequence at a time")
 
         for i, blk in enumerate(self.transformer.h):
             if blk.config.parallel_residual or not isinstance(blk.norm_1, RMSNorm):
-                raise NotImplementedError("batch size > 1 with parallel-residual (GPT-NeoX) blocks: the batched decode "
+                raise NotImplementedError(f"{what} with parallel-residual (GPT-NeoX) blocks: the batched decode "
                                           "runs RMSNorm / LLaMAMLP blocks only")
             if not isinstance(blk.mlp, LLaMAMLP):
-                raise NotImplementedError(f"batch size > 1 with a {type(blk.mlp).__name__} (sparse-MoE) block: the "
+                raise NotImplementedError(f"{what} with a {type(blk.mlp).__name__} (sparse-MoE) block: the "
                                           "routed expert kernels decode one sequence at a time")
             if blk.attn._forward_hooks or blk.mlp._forward_hooks or blk._forward_hooks:
-                raise NotImplementedError("batch size > 1 with forward hooks on a block (tensor parallelism): the "
+                raise NotImplementedError(f"{what} with forward hooks on a block (tensor parallelism): the "
                                           "fused GEMV + all-reduce decodes one sequence at a time")
             for name in ("attn.attn", "attn.proj", "mlp.fc_1", "mlp.fc_2", "mlp.proj"):
                 four_bit(blk.get_submodule(name), f"transformer.h.{i}.{name}")
         four_bit(self.lm_head, "lm_head")
         if not isinstance(self.transformer.ln_f, RMSNorm):
-            raise NotImplementedError("batch size > 1 needs an RMSNorm ln_f")
+            raise NotImplementedError(f"{what} needs an RMSNorm ln_f")
+
+    # Rows per speculative verify window (``decode_window``). The kernels take ops.MAX_WINDOW_ROWS = 8, and the cap
+    # stays there: measured at M = 2, 4, 8 (DESIGN §4.5d) the window attention launch costs 0.77 / 0.53 / 0.38 of M
+    # one-row launches on the Llama-2-7B geometry (0.77 / 0.55 / 0.41 with 8 query groups), so no M fails the criterion
+    # that capped MAX_BATCH. (Whether a long window pays is the drafter's acceptance rate, not this cap.)
+    MAX_WINDOW = 8
+
+    def decode_window(self, idx: torch.Tensor, pos0: torch.Tensor, *, embedded: Optional[torch.Tensor] = None,
+                      hidden_only: bool = False) -> torch.Tensor:
+        """One verify step of greedy speculative decoding: ``idx`` (M,) are M <= MAX_WINDOW consecutive tokens of ONE
+        sequence, row r at position ``pos0[0] + r`` (``pos0`` (1,) int64 on the device, read by the kernels: a
+        captured graph stays valid as it advances). Returns (M, padded_vocab) logits whose row r has the bits of the
+        one-row ``forward(idx[r], pos0 + r)`` after rows 0..r-1, and leaves the KV cache (slot 0) as those M steps
+        would: the batched step's layer sequence on the rows GEMVs (every weight streamed once for the M rows) with
+        ``ops.attention_decode_window`` once per block. Rows that a later round rejects leave stale K/V past the
+        accepted position; decode attention never reads past its row's position and the next window overwrites them.
+        ``embedded`` (M * n_embd bf16) replaces the embedding launch; ``hidden_only`` stops before ln_f / lm_head."""
+        M = idx.numel()
+        if not 1 <= M <= self.MAX_WINDOW:
+            raise NotImplementedError(f"window of {M} rows: the speculative verify step runs 1..{self.MAX_WINDOW} "
+                                      "rows")
+        self._rows_check("a speculative verify window")
+        c = self.config
+        if not ops.decode_fusable(c.head_size, c.rope_n_elem) or c.n_head // c.n_query_groups not in (1, 2, 4, 8):
+            raise NotImplementedError("a speculative verify window needs the fused decode attention's geometry "
+                                      "(head_size == rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group)")
+        if not idx.is_cuda:
+            _gpu_only("GPT.decode_window")
+        if self.mask_cache is None or self.transformer.h[0].attn.kv_cache is None:
+            raise TypeError("You need to call `gpt.set_kv_cache()`")
+        if pos0.numel() != 1 or pos0.dtype != torch.int64 or pos0.device != idx.device:
+            raise ValueError("pos0 must be one int64 position on the model's device")
+        cos, sin = self._rope_tables()
+        C = self.transformer.wte.weight.shape[1]
+        if embedded is not None:
+            if embedded.numel() != M * C or embedded.dtype != torch.bfloat16:
+                raise ValueError("embedded must hold M * n_embd bf16 values (the gathered wte rows of idx)")
+            x = embedded.view(M, C)
+        else:
+            x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(M, C)
+        for block in self.transformer.h:
+            x = block.decode_window(x, cos, sin, pos0)
+        if hidden_only:
+            return x
+        ln = self.transformer.ln_f
+        return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps, rows=True).view(M, -1)
 
     def _forward_batch(self, idx, input_pos, last_token_only, embedded, hidden_only) -> torch.Tensor:
         """The B > 1 forms of ``forward`` (its docstring). T = 1 per block: the rows qkv GEMV with norm_1 fused, the
@@ -246,6 +296,13 @@ class Block(nn.Module):
         """One batched decode step (GPT._forward_batch has checked the block): x (B, C), one token of each of B
         sequences at ``pos`` (B,), on the multi-row GEMVs; row b has the bits of ``forward`` on that sequence."""
         x = self.attn.decode_rows(x, cos, sin, pos, norm=self.norm_1, residual=x)
+        g = quantize.swiglu(self.mlp.fc_1, self.mlp.fc_2, x, self.norm_2, rows=True)
+        return _lin(self.mlp.proj, g, residual=x, rows=True)
+
+    def decode_window(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor) -> torch.Tensor:
+        """One verify window (GPT.decode_window has checked the block): x (M, C), M consecutive tokens of one sequence
+        from ``pos0`` (1,); ``decode_rows`` with the window attention in place of the per-sequence launches."""
+        x = self.attn.decode_window(x, cos, sin, pos0, norm=self.norm_1, residual=x)
         g = quantize.swiglu(self.mlp.fc_1, self.mlp.fc_2, x, self.norm_2, rows=True)
         return _lin(self.mlp.proj, g, residual=x, rows=True)
 
@@ -389,6 +446,31 @@ class CausalSelfAttention(nn.Module):
         for b in range(B):
             p = pos[b:b + 1]
             self._attend(qkv[b:b + 1], kv.k[b], kv.v[b], p, p, cos, sin, out=y[b:b + 1])
+        return _lin(self.proj, y, residual=residual, rows=True)
+
+    def decode_window(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor, *,
+                      norm: "RMSNorm", residual: torch.Tensor) -> torch.Tensor:
+        """Speculative verify window: x (M, C), M consecutive tokens of the sequence in cache slot 0 from ``pos0``
+        (1,). The qkv and the out-projection are the multi-row GEMVs; the M rows read one K / V, so attention is ONE
+        ``ops.attention_decode_window`` call with the split count of the one-row step (``ops.decode_splits`` of the
+        cache length: the bits of y depend on it, so the cache must be as long as the one ``generate`` would use)."""
+        c = self.config
+        H, G, hs = c.n_head, c.n_query_groups, c.head_size
+        M, dev = x.size(0), x.device
+        kv = self.kv_cache
+        qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
+        if kv.k.dtype != qkv.dtype:
+            kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
+        kc, vc = kv.k[0], kv.v[0]
+        n_splits = ops.decode_splits(G, H // G, hs, kc.size(-2))
+        wss = self.__dict__.setdefault("_window_ws", {})
+        ws = wss.get(M)
+        if ws is None or ws.key != (M, H, G, hs, n_splits) or ws.counters.device != dev:
+            ws = wss[M] = ops.AttentionWorkspace(M, H, G, hs, n_splits, dev)
+        cos = cos.to(device=dev, dtype=torch.float32).contiguous()
+        sin = sin.to(device=dev, dtype=torch.float32).contiguous()
+        y = ops.attention_decode_window(qkv, kc, vc, pos0, cos, sin, H, G, hs, c.rope_n_elem, 1.0 / math.sqrt(hs),
+                                        n_splits, workspace=ws)
         return _lin(self.proj, y, residual=residual, rows=True)
 
     def scaled_dot_product_attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,

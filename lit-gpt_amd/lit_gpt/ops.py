@@ -74,6 +74,8 @@ SIGNATURES = {
     "lga_attention": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "lga_attention_workspace_bytes": [_I, _I, _I, _I],
     "lga_attention_decode_fused": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "lga_attention_decode_window": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    "lga_spec_accept": [_P, _I, _I, _P, _P, _P, _P, _P],
     "lga_argmax": [_P, _I, _P, _P, _P, _P],
     "lga_q4_gemv_argmax_work_bytes": [_I, _I],
     "lga_q4_gemv_argmax_embed": [_P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P],
@@ -636,6 +638,64 @@ def attention_decode_fused(qkv, k_cache, v_cache, cache_pos, rope_pos, cos, sin,
         cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, n_head, n_query_groups, head_size, rope_n_elem, max_seq,
         n_splits, float(scale), _stream()))
     return y
+
+
+MAX_WINDOW_ROWS = 8  # rows per lga_attention_decode_window / lga_spec_accept launch
+
+
+def attention_decode_window(qkv, k_cache, v_cache, pos0, cos, sin, n_head, n_query_groups, head_size, rope_n_elem,
+                            scale, n_splits=1, workspace: Optional[AttentionWorkspace] = None, out=None):
+    """A speculative verify window: M = qkv.shape[0] (1..8) rows of ONE sequence at positions pos0[0] + r. RoPE +
+    KV-append + decode attention; y (M, H*hs) and the caches end bit-identical to M successive
+    ``attention_decode_fused`` calls with the same ``n_splits``. ``pos0`` (1,) int64 is read on the device."""
+    M = qkv.shape[0]
+    if qkv.dim() != 2 or not 1 <= M <= MAX_WINDOW_ROWS:
+        raise ValueError(f"attention_decode_window: qkv must be (M, (H + 2G) * hs) with 1 <= M <= {MAX_WINDOW_ROWS}, "
+                         f"got {tuple(qkv.shape)}")
+    if qkv.shape[1] != (n_head + 2 * n_query_groups) * head_size:
+        raise ValueError("attention_decode_window: qkv rows must hold (H + 2G) * hs values")
+    if pos0.numel() != 1:
+        raise ValueError("attention_decode_window: pos0 holds one position (row r sits at pos0 + r)")
+    max_seq = k_cache.shape[-2]
+    y = out if out is not None else torch.empty(M, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
+    if y.numel() != M * n_head * head_size:
+        raise ValueError("attention_decode_window: out must hold (M, H * hs) values")
+    if n_splits > 1:
+        if workspace is None:
+            raise ValueError("attention_decode_window: split attention needs an AttentionWorkspace(M, ...)")
+        if workspace.key != (M, n_head, n_query_groups, head_size, n_splits):
+            raise ValueError(f"attention_decode_window: workspace built for {workspace.key}, the call needs "
+                             f"{(M, n_head, n_query_groups, head_size, n_splits)}")
+        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
+    else:
+        ws = cnt = None
+    _check(load_library().lga_attention_decode_window(
+        _dev(qkv, "qkv", torch.bfloat16), _dev(k_cache, "k_cache", torch.bfloat16),
+        _dev(v_cache, "v_cache", torch.bfloat16), _dev(pos0, "pos0", torch.int64), _dev(cos, "cos", torch.float32),
+        _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, M, n_head,
+        n_query_groups, head_size, rope_n_elem, max_seq, n_splits, float(scale), _stream()))
+    return y
+
+
+def spec_accept(logits, window, out=None, token_inout=None, pos_inout=None):
+    """Greedy speculative acceptance in one launch. logits (M, n) bf16, window (M,) int32 (window[0] the last emitted
+    token, window[1:] the drafts): t_r = argmax(logits[r]) in ``argmax``'s order, a = the number of leading drafts
+    with window[r + 1] == t_r. Returns out (M + 1,) int32 = [a, t_0 .. t_a, -1 ...]; ``token_inout`` (1,) int32
+    receives t_a and ``pos_inout`` (1,) int64 advances by a + 1."""
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= MAX_WINDOW_ROWS:
+        raise ValueError(f"spec_accept: logits must be (M, n) with 1 <= M <= {MAX_WINDOW_ROWS}, "
+                         f"got {tuple(logits.shape)}")
+    M, n = logits.shape
+    if window.numel() != M:
+        raise ValueError(f"spec_accept: window holds {window.numel()} tokens for {M} rows of logits")
+    lp = _dev(logits, "logits", torch.bfloat16)
+    res = out if out is not None else torch.empty(M + 1, dtype=torch.int32, device=logits.device)
+    if res.numel() < M + 1:
+        raise ValueError("spec_accept: out needs M + 1 int32 values")
+    _check(load_library().lga_spec_accept(lp, M, n, _dev(window, "window", torch.int32), _dev(res, "out", torch.int32),
+                                          _opt(token_inout, "token_inout", torch.int32),
+                                          _opt(pos_inout, "pos_inout", torch.int64), _stream()))
+    return res
 
 
 class HeadWorkspace:

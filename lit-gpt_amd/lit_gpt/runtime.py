@@ -105,6 +105,76 @@ class DecodeGraph:
         self.chunk_graph.replay()
         return self.history
 
+    def reset(self, token, pos: int) -> None:
+        """Re-point the captured step at another (token, position): the next ``step()`` runs ``token`` (an int or a
+        one-element tensor) at ``pos`` over whatever the KV cache holds below ``pos``. The static buffers are
+        rewritten in place — the token, the position and the ``x_emb`` row the step reads instead of embedding — so
+        the graphs stay valid. A speculative draft model is re-pointed this way after a rejection."""
+        if torch.is_tensor(token):
+            self.token.view(-1).copy_(token.reshape(1))
+        else:
+            self.token.fill_(int(token))
+        self.pos.fill_(int(pos))
+        if self.fuse_embedding:
+            ops.embedding(self.token.view(-1), self.model.transformer.wte.weight, out=self.x_emb)
+
+
+class WindowDecodeGraph:
+    """The verify step of greedy speculative decoding (generate/speculative.py) for one sequence: device-resident
+    ``window`` (MAX_WINDOW,) int32 — ``window[0]`` the last emitted token, ``window[1:M]`` the drafts — and ``pos``
+    (1,), the position of ``window[0]``. A step over M = 1 + len(drafts) rows is embedding -> ``GPT.decode_window`` ->
+    ``ops.spec_accept``, every launch on one stream: one unbranched HIP graph per M in use, captured lazily (the first
+    step at an M runs eagerly and is then captured; the last windows of a run are shorter). ``spec_accept`` leaves
+    the accepted count and the emitted tokens in ``out``, writes the last of them to ``window[0]`` and advances
+    ``pos``, so the host reads ``out`` once per round and nothing per token. ``use_graph=False`` keeps every step
+    eager (tests A/B the two)."""
+
+    def __init__(self, model, first_token, first_pos: int, *, use_graph: bool = True) -> None:
+        wte = model.transformer.wte.weight
+        dev = wte.device
+        if not (wte.is_cuda and wte.dtype == torch.bfloat16 and wte.is_contiguous() and wte.shape[1] % 8 == 0):
+            raise NotImplementedError("speculative decoding needs a contiguous bf16 embedding table on the GPU with "
+                                      "n_embd % 8 == 0")
+        model._rows_check("a speculative verify window")  # refuse before any launch
+        self.model, self.use_graph = model, use_graph
+        self.max_rows = model.MAX_WINDOW
+        self.window = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)
+        self.window[:1].copy_(torch.as_tensor(first_token).reshape(1))
+        self.pos = torch.tensor([first_pos], dtype=torch.int64, device=dev)
+        self.out = torch.zeros(self.max_rows + 1, dtype=torch.int32, device=dev)
+        self.x_emb = torch.empty(self.max_rows, wte.shape[1], dtype=torch.bfloat16, device=dev)
+        self.graphs = {}
+
+    def _step_body(self, M: int) -> None:
+        model, w = self.model, self.window[:M]
+        x = ops.embedding(w, model.transformer.wte.weight, out=self.x_emb[:M])
+        logits = model.decode_window(w, self.pos, embedded=x)
+        ops.spec_accept(logits, w, out=self.out[:M + 1], token_inout=self.window[:1], pos_inout=self.pos)
+
+    def step(self, drafts=()):
+        """Verify ``drafts`` (a sequence of ints, or an int32 device tensor; at most MAX_WINDOW - 1 of them) after the
+        last emitted token. Returns (a, tokens): the number of accepted drafts and the a + 1 tokens this round emits."""
+        k = len(drafts)
+        M = k + 1
+        if M > self.max_rows:
+            raise ValueError(f"{k} drafts: a verify window holds at most {self.max_rows - 1}")
+        if k:
+            d = drafts if torch.is_tensor(drafts) else torch.tensor(list(drafts), dtype=torch.int32)
+            self.window[1:M].copy_(d)
+        g = self.graphs.get(M)
+        if g is not None:
+            g.replay()
+        else:
+            self._step_body(M)
+            if self.use_graph:
+                torch.cuda.synchronize(self.window.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._step_body(M)
+                self.graphs[M] = g
+        res = self.out[:M + 1].tolist()  # the round's one device -> host read
+        return res[0], res[1:res[0] + 2]
+
 
 class BatchDecodeGraph:
     """``DecodeGraph`` for B <= GPT.MAX_BATCH (4) sequences that decode in lock step (generate.base.generate_batch):
