@@ -225,6 +225,40 @@ int lga_attention_decode_window(const void* qkv, void* k_cache, void* v_cache, c
                                 const float* sin, int rope_rows, void* y, float* workspace, unsigned* counters, int M,
                                 int n_head, int n_query_groups, int head_size, int rope_n_elem, int max_seq,
                                 int n_splits, float scale, lga_stream_t stream);
+/* -- fp8 (OCP e4m3) KV cache -------------------------------------------------------------------------------------
+ * Per layer and slot: k_codes / v_codes (G, max_seq, 128) uint8 and k_scale / v_scale (G, max_seq) fp32. A row is the
+ * 128 bf16 values the bf16 cache would hold (k after RoPE). amax = max |x_i| = m 2^E, m in [0.5, 1); the scale is
+ * s = 2^e, e = E - 9 if m <= 0.875 else E - 8, clamped to [-126, 127] (the smallest power of two with amax / s <=
+ * 448); amax = 0 gives s = 1. code_i = e4m3fn(x_i / s), round to nearest even; the value read back is
+ * float(code_i) * s, exact in bf16. Rows with non-finite values or amax < 2^-100 are outside the contract. Every
+ * attention call reads K and V as the cache holds them, the call's own rows included.
+ * All four need head_size == rope_n_elem == 128; the two attention forms H/G in {1, 2, 4, 8}.
+ *
+ * lga_attention_decode_fused_kv8: lga_attention_decode_fused over fp8 caches; the new row's codes and scales are
+ * stored at cache_pos[0] (nothing at or past max_seq) and scored from registers as stored. */
+int lga_attention_decode_fused_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                   const int64_t* cache_pos, const int64_t* rope_pos, const float* cos,
+                                   const float* sin, int rope_rows, void* y, float* workspace, unsigned* counters,
+                                   int n_head, int n_query_groups, int head_size, int rope_n_elem, int max_seq,
+                                   int n_splits, float scale, lga_stream_t stream);
+/* lga_attention_decode_window over fp8 caches: y (M, H*hs), codes and scales bit-identical to M successive
+ * lga_attention_decode_fused_kv8 calls with the same n_splits. */
+int lga_attention_decode_window_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                    const int64_t* pos0, const float* cos, const float* sin, int rope_rows, void* y,
+                                    float* workspace, unsigned* counters, int M, int n_head, int n_query_groups,
+                                    int head_size, int rope_n_elem, int max_seq, int n_splits, float scale,
+                                    lga_stream_t stream);
+/* lga_rope_kv_append for fp8 caches (T rows): roped q to q_out (T, H, hs); k (roped) and v quantized into the codes
+ * and scales at row cache_pos[t] — the bits the decode forms store for the same qkv row. */
+int lga_kv8_rope_append(const void* qkv, void* q_out, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                        const int64_t* cache_pos, const int64_t* rope_pos, const float* cos, const float* sin,
+                        int rope_rows, int T, int n_head, int n_query_groups, int head_size, int rope_n_elem,
+                        int max_seq, lga_stream_t stream);
+/* Rows [0, n) of every group of one slot's codes and scales -> k_out / v_out (G, n, 128) bf16 = float(code) * scale
+ * (exact). The cached prefill (T > 1) expands the cache with it and runs lga_attention over the result. */
+int lga_kv8_dequantize(const void* k_codes, const void* v_codes, const float* k_scale, const float* v_scale,
+                       void* k_out, void* v_out, int n_query_groups, int n, int head_size, int max_seq,
+                       lga_stream_t stream);
 /* Greedy speculative acceptance after the window's lm_head: logits (M, n) bf16 contiguous, window (M) int32
  * (window[0] the last emitted token, window[1..] the drafts). t_r = argmax of row r in lga_argmax's order; a = the
  * largest a <= M - 1 with window[r + 1] == t_r for all r < a. out (M + 1) int32: out[0] = a, out[1..a+1] = t_0..t_a,

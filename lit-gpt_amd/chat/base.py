@@ -132,7 +132,8 @@ def prompt_config(checkpoint_dir: Path, tokenizer) -> Tuple[str, Tuple[List[int]
 @torch.inference_mode()
 def main(*, top_k: Optional[int] = 200, temperature: float = 0.8,
          checkpoint_dir: Path = Path("checkpoints/meta-llama/Llama-2-7b-chat-hf"),
-         quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False) -> None:
+         quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
+         kv_cache: str = "bf16") -> None:
     precision = precision or "bf16-true"
     if precision != "bf16-true":
         raise NotImplementedError("the MI355X path computes in bf16 (precision bf16-true)")
@@ -144,7 +145,7 @@ def main(*, top_k: Optional[int] = 200, temperature: float = 0.8,
     config = Config.from_json(checkpoint_dir / "lit_config.json")
     checkpoint_path = checkpoint_dir / "lit_model.pth"
     print(f"Loading model {str(checkpoint_path)!r} with {config.__dict__}", file=sys.stderr)
-    model = build_model(config, quantize=quantize, device=device, checkpoint_path=checkpoint_path)
+    model = build_model(config, quantize=quantize, device=device, checkpoint_path=checkpoint_path, kv_cache=kv_cache)
     tokenizer = Tokenizer(checkpoint_dir)
     system_prompt, stop_tokens = prompt_config(checkpoint_dir, tokenizer)
     torch.manual_seed(1234)
@@ -176,9 +177,11 @@ def _cli(argv=None) -> None:
     p.add_argument("--quantize", default=None)
     p.add_argument("--precision", default=None)
     p.add_argument("--compile", action="store_true")
+    p.add_argument("--kv_cache", default="bf16", choices=["bf16", "fp8"],
+                   help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per row (0.516 x the bytes)")
     a = p.parse_args(argv)
     main(top_k=a.top_k, temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize,
-         precision=a.precision, compile=a.compile)
+         precision=a.precision, compile=a.compile, kv_cache=a.kv_cache)
 
 
 if __name__ == "__main__":

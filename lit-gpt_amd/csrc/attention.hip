@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "decode_ops.h"
+#include "kv8_ops.h"
 
 namespace lga {
 
@@ -53,6 +54,27 @@ __device__ __forceinline__ uint4 ld_kv(const uint16_t* p) {
   return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// KV8 (fp8 caches): a key / value row is HS e4m3 codes (8 B per lane of the same HS / 8-lane row group)
+// plus one fp32 power-of-two scale; the codes expand to packed bf16 (K, for the same v_dot2 chain) and fp32 (V) in
+// registers, unscaled: the row's scale multiplies the score, s_j (q . k8_j), and the P.V weight, e sv_j — exact, so
+// the arithmetic is the bf16 cache's on the dequantized values.
+template <bool NT = true>
+__device__ __forceinline__ uint2 ld_kv8(const uint8_t* p) {
+  typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+  if constexpr (!NT) return *(const uint2*)p;
+  const u32x2_t v = __builtin_nontemporal_load((const u32x2_t*)p);
+  return make_uint2(v.x, v.y);
+}
+template <bool KV8>
+struct kv_regs {  // one lane's share of a K or V row in flight
+  uint4 d;
+};
+template <>
+struct kv_regs<true> {
+  uint2 d;
+  float s;
+};
+
 // FUSED (decode, T = 1): q, k, v come straight from the qkv projection row; every workgroup ropes its group's
 // q heads itself, and the workgroup whose split owns the new position p ropes k, appends k and v to the cache
 // at p (KVCache.forward, lit_gpt/model.py:788-795) and scores that key from registers — replacing the separate
@@ -71,13 +93,15 @@ __device__ __forceinline__ uint4 ld_kv(const uint16_t* p) {
 #define LGA_ATTN_WIN_NT 0  // lab A/B: 1 = the one-row kernel's nt loads in the window kernel too
 #endif
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE, bool WINDOW = false>
+template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE, bool WINDOW = false, bool KV8 = false>
 __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc,
                                           uint16_t* __restrict__ vc, const int64_t* __restrict__ input_pos,
                                           uint16_t* __restrict__ y, float* __restrict__ ws,
                                           unsigned* __restrict__ cnt, int n_head, int max_seq, float scale,
                                           const int64_t* __restrict__ rope_pos, const float* __restrict__ cos,
-                                          const float* __restrict__ sin, int rope_rows, int hsplit) {
+                                          const float* __restrict__ sin, int rope_rows, int hsplit,
+                                          float* __restrict__ ksc = nullptr, float* __restrict__ vsc = nullptr) {
+  static_assert(!KV8 || (FUSED && HS == 128), "the fp8 cache serves the fused decode forms");
   constexpr int LPR = HS / 8;    // lanes per key row
   constexpr int RGW = 64 / LPR;  // row groups per wave
   constexpr int RG = NW * RGW;   // row groups per workgroup
@@ -112,13 +136,25 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   }
   const uint16_t* kbase = kc + (size_t)g * max_seq * HS + sub * 8;
   const uint16_t* vbase = vc + (size_t)g * max_seq * HS + sub * 8;
+  // (KV8: the same element offsets in bytes, and the group's scale rows)
+  const uint8_t* kbase8 = (const uint8_t*)kc + (size_t)g * max_seq * HS + sub * 8;
+  const uint8_t* vbase8 = (const uint8_t*)vc + (size_t)g * max_seq * HS + sub * 8;
+  const float* ksg = KV8 ? ksc + (size_t)g * max_seq : nullptr;
+  const float* vsg = KV8 ? vsc + (size_t)g * max_seq : nullptr;
   // clamped duplicate rows (past k_end) are masked in consume() and hit in cache
-  auto fetch = [&](uint4 (&kv)[UNR], uint4 (&vv)[UNR], int j0) {
+  auto fetch = [&](kv_regs<KV8> (&kv)[UNR], kv_regs<KV8> (&vv)[UNR], int j0) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int j = max(min(j0 + u * RG, k_end - 1), 0);
-      kv[u] = ld_kv<!WINDOW || LGA_ATTN_WIN_NT>(kbase + (size_t)j * HS);
-      vv[u] = ld_kv<!WINDOW || LGA_ATTN_WIN_NT>(vbase + (size_t)j * HS);
+      if constexpr (KV8) {
+        kv[u].d = ld_kv8<!WINDOW || LGA_ATTN_WIN_NT>(kbase8 + (size_t)j * HS);
+        vv[u].d = ld_kv8<!WINDOW || LGA_ATTN_WIN_NT>(vbase8 + (size_t)j * HS);
+        kv[u].s = ksg[j];
+        vv[u].s = vsg[j];
+      } else {
+        kv[u].d = ld_kv<!WINDOW || LGA_ATTN_WIN_NT>(kbase + (size_t)j * HS);
+        vv[u].d = ld_kv<!WINDOW || LGA_ATTN_WIN_NT>(vbase + (size_t)j * HS);
+      }
     }
   };
   const int j_first = k_lo + rg;
@@ -162,7 +198,7 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   // the first K/V batch AFTER the RoPE: issued beside q (ahead of the RoPE's wait) every split's first loads leave
   // in one burst at kernel start, measured 0.25-0.3 us slower per launch (tools/attn_ab.py, round 5)
   __builtin_amdgcn_sched_barrier(0);
-  uint4 ka[UNR], va[UNR], kb[UNR], vb[UNR];
+  kv_regs<KV8> ka[UNR], va[UNR], kb[UNR], vb[UNR];
   if (PIPE) fetch(ka, va, j_first);
   LGA_TRACE(2);
   // m starts at a finite floor, not -inf: every row group runs the split's step count, so one whose keys are all
@@ -178,14 +214,16 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
     for (int i = 0; i < 8; ++i) o[h][i] = 0.0f;
   }
   // one step = UNR keys per row group: scores, online-softmax rescale, P.V (masked keys score -inf)
-  auto consume = [&](const uint4 (&kv)[UNR], const uint4 (&vv)[UNR], int j0) {
+  auto consume = [&](const kv_regs<KV8> (&kv)[UNR], const kv_regs<KV8> (&vv)[UNR], int j0) {
 #pragma unroll
     for (int h = 0; h < QPK; ++h) {
       float s[UNR];
       float mx = m[h];
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
-        const float sd = row_group_sum<LPR>(dot8(qp[h], kv[u])) * sl2;  // whole row group active: DPP inside it
+        float sd;  // whole row group active: DPP inside it
+        if constexpr (KV8) sd = row_group_sum<LPR>(dot8(qp[h], kv8_bf16x8(kv[u].d))) * (kv[u].s * sl2);
+        else sd = row_group_sum<LPR>(dot8(qp[h], kv[u].d)) * sl2;
         s[u] = (j0 + u * RG < k_end) ? sd : -INFINITY;
         mx = fmaxf(mx, s[u]);
       }
@@ -198,9 +236,16 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
         const float e = __builtin_amdgcn_exp2f(s[u] - mx);  // masked keys: exp(-inf) = 0
         l[h] += e;
         float vf[8];
-        unpack8(vv[u], vf);
+        if constexpr (KV8) {
+          kv8_f32x8(vv[u].d, vf);
+          const float ev = e * vv[u].s;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) o[h][i] = fmaf(e, vf[i], o[h][i]);
+          for (int i = 0; i < 8; ++i) o[h][i] = fmaf(ev, vf[i], o[h][i]);
+        } else {
+          unpack8(vv[u].d, vf);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o[h][i] = fmaf(e, vf[i], o[h][i]);
+        }
       }
       m[h] = mx;
     }
@@ -228,23 +273,43 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   LGA_TRACE(3);
   if (FUSED && owns_new && rg == 0) {  // the new key/value: rope k, append both to the cache, score from registers
     const uint16_t* kvrow = q + ((size_t)g * (QPKT + 2) + QPKT) * HS + sub * 8;
-    const uint4 kr = rope8(*(const uint4*)kvrow, cs, sn, sub);
+    uint4 kr = rope8(*(const uint4*)kvrow, cs, sn, sub);
     const uint4 vr = *(const uint4*)(kvrow + HS);
-    if (!WINDOW && hsi == 0) {  // one head slice appends; the others score the same key from their registers
-      *(uint4*)(kc + ((size_t)g * max_seq + p) * HS + sub * 8) = kr;
-      *(uint4*)(vc + ((size_t)g * max_seq + p) * HS + sub * 8) = vr;
-    }
     float vf[8];
-    unpack8(vr, vf);
+    float ksn = 1.0f, vsn = 1.0f;  // KV8: the new row's scales
+    if constexpr (KV8) {
+      // the row is scored as the cache holds it: quantized here (every head slice; the row group is whole), its codes
+      // expanded again for the score
+      const uint2 k8 = kv8_quantize8(kr, ksn), v8 = kv8_quantize8(vr, vsn);
+      if (!WINDOW && hsi == 0) {  // one head slice appends
+        *(uint2*)((uint8_t*)kc + ((size_t)g * max_seq + p) * HS + sub * 8) = k8;
+        *(uint2*)((uint8_t*)vc + ((size_t)g * max_seq + p) * HS + sub * 8) = v8;
+        if (sub == 0) {
+          ksc[(size_t)g * max_seq + p] = ksn;
+          vsc[(size_t)g * max_seq + p] = vsn;
+        }
+      }
+      kr = kv8_bf16x8(k8);
+      kv8_f32x8(v8, vf);
+    } else {
+      if (!WINDOW && hsi == 0) {  // one head slice appends; the others score the same key from their registers
+        *(uint4*)(kc + ((size_t)g * max_seq + p) * HS + sub * 8) = kr;
+        *(uint4*)(vc + ((size_t)g * max_seq + p) * HS + sub * 8) = vr;
+      }
+      unpack8(vr, vf);
+    }
 #pragma unroll
     for (int h = 0; h < QPK; ++h) {
-      const float s = row_group_sum<LPR>(dot8(qp[h], kr)) * sl2;
+      float s;
+      if constexpr (KV8) s = row_group_sum<LPR>(dot8(qp[h], kr)) * (ksn * sl2);
+      else s = row_group_sum<LPR>(dot8(qp[h], kr)) * sl2;
       const float mx = fmaxf(m[h], s);
       const float c = __builtin_amdgcn_exp2f(m[h] - mx);
       const float e = __builtin_amdgcn_exp2f(s - mx);
       l[h] = l[h] * c + e;
+      const float ev = KV8 ? e * vsn : e;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[h][i] = fmaf(e, vf[i], o[h][i] * c);
+      for (int i = 0; i < 8; ++i) o[h][i] = fmaf(ev, vf[i], o[h][i] * c);
       m[h] = mx;
     }
   }
@@ -393,6 +458,21 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel(const uint16_t* __restric
                                                    cos, sin, rope_rows, hsplit);
 }
 
+// the fp8-cache instantiations (FUSED one-row and WINDOW): attn_kernel plus the two scale arrays
+template <int HS, int QPK, int UNR, int NW, bool PIPE, bool WINDOW>
+__global__ void __launch_bounds__(NW * 64) attn_kernel_kv8(const uint16_t* __restrict__ q, uint8_t* __restrict__ kc,
+                                                       uint8_t* __restrict__ vc, float* __restrict__ ksc,
+                                                       float* __restrict__ vsc, const int64_t* __restrict__ input_pos,
+                                                       uint16_t* __restrict__ y, float* __restrict__ ws,
+                                                       unsigned* __restrict__ cnt, int n_head, int max_seq, float scale,
+                                                       const int64_t* __restrict__ rope_pos,
+                                                       const float* __restrict__ cos, const float* __restrict__ sin,
+                                                       int rope_rows, int hsplit) {
+  attn_body<HS, QPK, UNR, NW, true, PIPE, WINDOW, true>(q, (uint16_t*)kc, (uint16_t*)vc, input_pos, y, ws, cnt, n_head,
+                                                        max_seq, scale, rope_pos, cos, sin, rope_rows, hsplit, ksc,
+                                                        vsc);
+}
+
 // The window's KV-append: roped k and v of row r into cache row pos0[0] + r of every group, with the fused kernel's
 // own rope8 on the same operands (the same bits it stores at T = 1). Grid (G, M), one wave: lanes 0..HS/8-1 move k,
 // the next HS/8 move v. A row at or past max_seq stores nothing.
@@ -420,6 +500,41 @@ __global__ void __launch_bounds__(64) window_append_kernel(const uint16_t* __res
   } else {
     *(uint4*)(vc + dst) = *(const uint4*)(kvrow + HS);
   }
+}
+
+// window_append_kernel for fp8 caches: row group 0 ropes k, row group 1 holds v, both quantize their row with the
+// fused kernel's kv8_quantize8 on the same operands (the same codes and scales it stores at T = 1).
+__global__ void __launch_bounds__(64) window_append_kv8_kernel(const uint16_t* __restrict__ qkv, uint8_t* __restrict__ kc,
+                                                              uint8_t* __restrict__ vc, float* __restrict__ ksc,
+                                                              float* __restrict__ vsc, const int64_t* __restrict__ pos0,
+                                                              const float* __restrict__ cos,
+                                                              const float* __restrict__ sin, int rope_rows, int n_head,
+                                                              int max_seq) {
+  constexpr int HS = 128, LPR = HS / 8;
+  const int g = blockIdx.x, G = gridDim.x, r = blockIdx.y, qpk = n_head / G;
+  const int lane = threadIdx.x, sub = lane % LPR;
+  const long p = pos0[0] + r;
+  if (lane >= 2 * LPR || p < 0 || p >= max_seq) return;
+  const uint16_t* kvrow = qkv + ((size_t)r * (n_head + 2 * G) + (size_t)g * (qpk + 2) + qpk) * HS + sub * 8;
+  const bool is_k = lane < LPR;
+  uint4 x;
+  if (is_k) {
+    const long rp = min(max(p, 0L), (long)rope_rows - 1);
+    float cs[8], sn[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      cs[i] = cos[(size_t)rp * HS + sub * 8 + i];
+      sn[i] = sin[(size_t)rp * HS + sub * 8 + i];
+    }
+    x = rope8(*(const uint4*)kvrow, cs, sn, sub);
+  } else {
+    x = *(const uint4*)(kvrow + HS);
+  }
+  float s;
+  const uint2 c8 = kv8_quantize8(x, s);
+  const size_t row = (size_t)g * max_seq + p;
+  *(uint2*)((is_k ? kc : vc) + row * HS + sub * 8) = c8;
+  if (sub == 0) (is_k ? ksc : vsc)[row] = s;
 }
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -974,13 +1089,19 @@ __global__ void __launch_bounds__(512, 1) attn_prefill_pair_kernel(const uint16_
 #define LGA_ATTN_Q8 2, 4
 #endif
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool WINDOW = false>
+template <int HS, int QPK, int UNR, int NW, bool FUSED, bool WINDOW = false, bool KV8 = false>
 static void launch_one(dim3 grid, hipStream_t stream, const void* q, void* kc, void* vc, const int64_t* pos, void* y,
                        float* ws, unsigned* cnt, int H, int max_seq, float scale, const int64_t* rope_pos,
-                       const float* cos, const float* sin, int rope_rows, int hsplit) {
-  attn_kernel<HS, QPK, UNR, NW, FUSED, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>((const uint16_t*)q, (uint16_t*)kc, (uint16_t*)vc,
-                                                                     pos, (uint16_t*)y, ws, cnt, H, max_seq, scale,
-                                                                     rope_pos, cos, sin, rope_rows, hsplit);
+                       const float* cos, const float* sin, int rope_rows, int hsplit, float* ksc, float* vsc) {
+  if constexpr (KV8) {
+    attn_kernel_kv8<HS, QPK, UNR, NW, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
+        (const uint16_t*)q, (uint8_t*)kc, (uint8_t*)vc, ksc, vsc, pos, (uint16_t*)y, ws, cnt, H, max_seq, scale,
+        rope_pos, cos, sin, rope_rows, hsplit);
+  } else {
+    attn_kernel<HS, QPK, UNR, NW, FUSED, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
+        (const uint16_t*)q, (uint16_t*)kc, (uint16_t*)vc, pos, (uint16_t*)y, ws, cnt, H, max_seq, scale, rope_pos, cos,
+        sin, rope_rows, hsplit);
+  }
 }
 
 // head slices per query group: split a group's heads over more workgroups while the launch would fill at most half
@@ -998,15 +1119,15 @@ static int attn_hsplit(int T, int G, int qpk, int n_splits) {
   return h;
 }
 
-template <int HS, bool FUSED, bool WINDOW = false>
+template <int HS, bool FUSED, bool WINDOW = false, bool KV8 = false>
 static int launch_hs(const void* q, void* kc, void* vc, const int64_t* pos, void* y, float* ws, unsigned* cnt, int T,
                      int H, int G, int max_seq, int n_splits, float scale, const int64_t* rope_pos, const float* cos,
-                     const float* sin, int rope_rows, hipStream_t stream) {
+                     const float* sin, int rope_rows, hipStream_t stream, float* ksc = nullptr, float* vsc = nullptr) {
   const int hsplit = attn_hsplit(WINDOW ? 1 : T, G, H / G, n_splits);  // a window row: the slices of its T = 1 launch
   const dim3 grid(n_splits, G * hsplit, T);
 #define LGA_ATTN(QPK, CFG)                                                                                        \
-  launch_one<HS, QPK, CFG, FUSED, WINDOW>(grid, stream, q, kc, vc, pos, y, ws, cnt, H, max_seq, scale, rope_pos, cos, sin, \
-                                  rope_rows, hsplit)
+  launch_one<HS, QPK, CFG, FUSED, WINDOW, KV8>(grid, stream, q, kc, vc, pos, y, ws, cnt, H, max_seq, scale, rope_pos, cos, \
+                                       sin, rope_rows, hsplit, ksc, vsc)
   switch (H / G / hsplit) {
     case 1:  // one head per group: 8 waves x 2 keys in flight when the groups are few (TP ranks: G = 4 7.9 vs 8.2 us,
              // G = 8 8.0 vs 8.7 at 16 splits; profiles/r04u_attn_head_slices.txt), else 4 x 4 (Llama-2-7B, G = 32)
@@ -1135,6 +1256,55 @@ extern "C" int lga_attention_decode_window(const void* qkv, void* k_cache, void*
   if (rc) return rc;
   LGA_LAUNCH_RETURN();
 }
+
+// The two decode forms over fp8 (e4m3) caches: k_codes / v_codes (G, max_seq, 128) uint8, k_scale / v_scale
+// (G, max_seq) fp32 powers of two. The new row(s) are quantized on the way in and scored as the cache holds them.
+#define LGA_KV8_COMMON(NAME)                                                                                         \
+  LGA_CHECK_ARG(n_query_groups > 0 && n_head % n_query_groups == 0, NAME ": bad head geometry");                     \
+  LGA_CHECK_ARG(head_size == 128 && rope_n_elem == 128, NAME ": needs head_size == rope_n_elem == 128");            \
+  {                                                                                                                  \
+    const int qpk = n_head / n_query_groups;                                                                         \
+    LGA_CHECK_ARG(qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8, NAME ": q_per_kv must be 1, 2, 4 or 8");             \
+  }                                                                                                                  \
+  LGA_CHECK_ARG(rope_rows > 0 && max_seq > 0, NAME ": empty rope cache or kv cache");                                \
+  LGA_CHECK_ARG(n_splits >= 1 && n_splits <= 256, NAME ": n_splits must be in [1, 256]");                            \
+  LGA_CHECK_ARG(n_splits == 1 || (workspace && counters), NAME ": split attention needs workspace + counters")
+
+extern "C" int lga_attention_decode_fused_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale,
+                                              float* v_scale, const int64_t* cache_pos, const int64_t* rope_pos,
+                                              const float* cos, const float* sin, int rope_rows, void* y,
+                                              float* workspace, unsigned* counters, int n_head, int n_query_groups,
+                                              int head_size, int rope_n_elem, int max_seq, int n_splits, float scale,
+                                              hipStream_t stream) {
+  LGA_CHECK_ARG(qkv && k_codes && v_codes && k_scale && v_scale && cache_pos && rope_pos && cos && sin && y,
+                "lga_attention_decode_fused_kv8: null pointer");
+  LGA_KV8_COMMON("lga_attention_decode_fused_kv8");
+  const int rc = lga::launch_hs<128, true, false, true>(qkv, k_codes, v_codes, cache_pos, y, workspace, counters, 1,
+                                                        n_head, n_query_groups, max_seq, n_splits, scale, rope_pos,
+                                                        cos, sin, rope_rows, stream, k_scale, v_scale);
+  if (rc) return rc;
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_attention_decode_window_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale,
+                                               float* v_scale, const int64_t* pos0, const float* cos, const float* sin,
+                                               int rope_rows, void* y, float* workspace, unsigned* counters, int M,
+                                               int n_head, int n_query_groups, int head_size, int rope_n_elem,
+                                               int max_seq, int n_splits, float scale, hipStream_t stream) {
+  LGA_CHECK_ARG(qkv && k_codes && v_codes && k_scale && v_scale && pos0 && cos && sin && y,
+                "lga_attention_decode_window_kv8: null pointer");
+  LGA_CHECK_ARG(M >= 1 && M <= 8, "lga_attention_decode_window_kv8: M must be in [1, 8]");
+  LGA_KV8_COMMON("lga_attention_decode_window_kv8");
+  lga::window_append_kv8_kernel<<<dim3(n_query_groups, M), 64, 0, stream>>>(
+      (const uint16_t*)qkv, (uint8_t*)k_codes, (uint8_t*)v_codes, k_scale, v_scale, pos0, cos, sin, rope_rows, n_head,
+      max_seq);
+  const int rc = lga::launch_hs<128, true, true, true>(qkv, k_codes, v_codes, pos0, y, workspace, counters, M, n_head,
+                                                       n_query_groups, max_seq, n_splits, scale, pos0, cos, sin,
+                                                       rope_rows, stream, k_scale, v_scale);
+  if (rc) return rc;
+  LGA_LAUNCH_RETURN();
+}
+#undef LGA_KV8_COMMON
 
 #ifdef LGA_ATTN_TRACE
 extern "C" int lga_attn_trace_read(unsigned long long* host, int n) {

@@ -15,6 +15,11 @@ reduced on the device, the logits never reach the host. Prints ONE JSON line:
 ``max_kl`` (KL(MODE model || evaluated model) per position, nats) and ``top1_agree`` (share of positions where both
 pick the same token), from ``lit_gpt.score.compare_tokens``.
 
+``--kv_cache fp8`` scores every window as a prefill through an fp8 (e4m3) KV cache (``input_pos = arange(T)``), so
+``nll`` / ``ppl`` reflect the quantized K / V: the way to see what that cache format costs on a real checkpoint.
+Without it (or with ``--kv_cache bf16``) the windows take the no-cache forward, as before. ``--against`` models keep
+the no-cache forward.
+
 ``--synthetic NAME`` is a random-init model of a registered config with seeded token ids, as ``generate/base.py
 --synthetic``: it measures speed and orders the formats by their distance to bf16 on THIS build's arithmetic; it is not
 the loss of a trained checkpoint.
@@ -40,8 +45,10 @@ from lit_gpt import Config, score  # noqa: E402
 
 
 @torch.inference_mode()
-def evaluate(model, tokens, *, max_len: int, prefix_token: int, min_context: int = 1, against=None) -> dict:
-    """Score ``tokens`` (a sequence of ids) window by window; the dict the command prints."""
+def evaluate(model, tokens, *, max_len: int, prefix_token: int, min_context: int = 1, against=None,
+             cached: bool = False) -> dict:
+    """Score ``tokens`` (a sequence of ids) window by window; the dict the command prints. ``cached``: every window is
+    a prefill through the model's KV cache, so ``nll`` / ``ppl`` see its format (``--kv_cache fp8``)."""
     toks = [int(t) for t in tokens]
     nll, windows, done, dt = 0.0, 0, 0, 0.0
     kls, agree = [], 0
@@ -50,7 +57,7 @@ def evaluate(model, tokens, *, max_len: int, prefix_token: int, min_context: int
         window = input_ids + [toks[done - 1]]
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        lp, _, hidden = score.score_tokens(model, window, n_scored, return_hidden=True)
+        lp, _, hidden = score.score_tokens(model, window, n_scored, return_hidden=True, cached=cached)
         nll -= float(lp.double().sum())  # (a device-to-host copy: the window's work is done)
         dt += time.perf_counter() - t0
         windows += 1
@@ -70,7 +77,7 @@ def evaluate(model, tokens, *, max_len: int, prefix_token: int, min_context: int
 def main(*, checkpoint_dir: Optional[Path] = None, text: Optional[Path] = None, tokens: Optional[Path] = None,
          synthetic: Optional[str] = None, n_tokens: int = 2048, quantize: Optional[str] = None,
          precision: Optional[str] = None, max_seq_length: Optional[int] = None, min_context: int = 1,
-         against: Optional[str] = None) -> dict:
+         against: Optional[str] = None, kv_cache: str = "bf16") -> dict:
     from generate.base import build_model
 
     precision = precision or "bf16-true"
@@ -107,14 +114,17 @@ def main(*, checkpoint_dir: Optional[Path] = None, text: Optional[Path] = None, 
             ids = np.load(tokens, allow_pickle=False).reshape(-1).astype(np.int64).tolist()
     max_len = max_seq_length or config.block_size
 
-    def build(mode: Optional[str]):
+    def build(mode: Optional[str], kv: str = "bf16"):
         return build_model(config, quantize=None if mode in (None, "bf16") else mode, device=device,
-                           checkpoint_path=checkpoint_path, max_seq_length=max_len, dtype=dtype)
+                           checkpoint_path=checkpoint_path, max_seq_length=max_len, dtype=dtype, kv_cache=kv)
 
     print(f"Loading model {str(checkpoint_path or synthetic)!r} ({quantize or precision})", file=sys.stderr)
-    model = build(quantize)
+    model = build(quantize, kv_cache)
     other = build(against) if against is not None else None
-    out = evaluate(model, ids, max_len=max_len, prefix_token=prefix, min_context=min_context, against=other)
+    # fp8: each window is scored as a cached prefill, so the figures carry the cache's quantization; bf16 keeps the
+    # no-cache forward (bit for bit the figures without the flag)
+    out = evaluate(model, ids, max_len=max_len, prefix_token=prefix, min_context=min_context, against=other,
+                   cached=kv_cache == "fp8")
     print(json.dumps(out))
     return out
 
@@ -131,10 +141,13 @@ def _cli(argv=None) -> None:
     p.add_argument("--max_seq_length", type=int, default=None)
     p.add_argument("--min_context", type=int, default=1)
     p.add_argument("--against", default=None, help="bf16 or a quantize mode: also report KL and top-1 agreement")
+    p.add_argument("--kv_cache", default="bf16", choices=["bf16", "fp8"],
+                   help="fp8: score every window as a prefill through an fp8 (e4m3) KV cache — what that cache "
+                        "format costs in nll / ppl on this checkpoint")
     a = p.parse_args(argv)
     main(checkpoint_dir=a.checkpoint_dir, text=a.text, tokens=a.tokens, synthetic=a.synthetic, n_tokens=a.n_tokens,
          quantize=a.quantize, precision=a.precision, max_seq_length=a.max_seq_length, min_context=a.min_context,
-         against=a.against)
+         against=a.against, kv_cache=a.kv_cache)
 
 
 if __name__ == "__main__":

@@ -225,7 +225,7 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
                          eos_id=eos_id, use_graph=use_graph, rng=None if rngs is None else rngs[0])]
     kv = model.transformer.h[0].attn.kv_cache
     if kv is None or kv.k.size(0) < B:
-        model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.k.dtype)
+        model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.cache_dtype)
     firsts = []
     for b, prompt in enumerate(prompts):  # the single path's prefill (next_token), on slot b
         T = prompt.size(0)
@@ -253,10 +253,14 @@ def _check_collectives() -> None:
         comm.check_errors()
 
 
+# --kv_cache choices -> GPT.set_kv_cache dtype (None: the activation dtype)
+KV_CACHE_DTYPES = {"bf16": None, "fp8": torch.float8_e4m3fn}
+
+
 def build_model(config: Config, *, quantize: Optional[str], device: torch.device, seed: int = 1234,
                 checkpoint_path: Optional[Path] = None, max_seq_length: Optional[int] = None,
                 fabric=None, rope_positions: str = "reference", prefill_rows: Optional[int] = None,
-                dtype: torch.dtype = torch.bfloat16) -> GPT:
+                dtype: torch.dtype = torch.bfloat16, kv_cache: str = "bf16") -> GPT:
     """Instantiate on the meta device, then materialise (load, or random-init as GPT._init_weights) the float
     weights on the GPU in the model's parameter order; with ``fabric`` (world_size / global_rank, generate/tp.py)
     every block is sharded (``tensor_parallel_block``) and quantized as soon as its weights exist, so a rank holds
@@ -269,7 +273,14 @@ def build_model(config: Config, *, quantize: Optional[str], device: torch.device
     (generate/base.py:153-157): positions above 256 round to bf16. ``"exact"`` keeps fp32 positions.
     ``prefill_rows`` (the prompt length about to be served) is accepted for API stability; the prefill GEMMs are
     hand-written (csrc/gemm_q4f.hip) and need no per-shape tuning or warm-up. ``dtype`` float32 is the reference's
-    ``--precision 32-true`` (GPT-NeoX family, csrc/fp32.hip; no quantization, no TP)."""
+    ``--precision 32-true`` (GPT-NeoX family, csrc/fp32.hip; no quantization, no TP). ``kv_cache="fp8"`` builds the
+    e4m3 KV cache (``GPT.set_kv_cache(dtype=torch.float8_e4m3fn)``) in place of one in ``dtype``."""
+    if kv_cache not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache must be one of {sorted(KV_CACHE_DTYPES)}, got {kv_cache!r}")
+    if kv_cache == "fp8" and (dtype == torch.float32 or (fabric is not None and fabric.world_size > 1)):
+        # (before any weight is materialised; GPT.set_kv_cache refuses the same, and the geometry, at the cache)
+        raise NotImplementedError("--kv_cache fp8 runs with bf16 activations on one device (no 32-true, no tensor "
+                                  "parallelism)")
     if dtype not in (torch.bfloat16, torch.float32):
         raise NotImplementedError(f"precision with dtype {dtype}: the MI355X path computes in bf16 or fp32")
     if dtype == torch.float32 and (quantize is not None or (fabric is not None and fabric.world_size > 1)):
@@ -356,7 +367,7 @@ def build_model(config: Config, *, quantize: Optional[str], device: torch.device
         model.cos, model.sin = model.rope_cache(device=device)
     finally:
         torch.set_default_dtype(prev)
-    model.set_kv_cache(batch_size=1, device=device, dtype=dtype)
+    model.set_kv_cache(batch_size=1, device=device, dtype=KV_CACHE_DTYPES[kv_cache] or dtype)
     ops.preload_kernels()  # the runtime would otherwise build each prefill kernel inside the first prompt
     return model.eval()
 
@@ -366,7 +377,8 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
          top_k: Optional[int] = 200, temperature: float = 0.8,
          checkpoint_dir: Path = Path("checkpoints/stabilityai/stablelm-base-alpha-3b"),
          quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
-         synthetic: Optional[str] = None, prompt_len: int = 16, batch_size: int = 1) -> None:
+         synthetic: Optional[str] = None, prompt_len: int = 16, batch_size: int = 1,
+         kv_cache: str = "bf16") -> None:
     precision = precision or "bf16-true"
     if not 1 <= batch_size <= MAX_BATCH:
         raise NotImplementedError(f"--batch_size {batch_size}: the batched decode runs 1..{MAX_BATCH} sequences")
@@ -394,7 +406,8 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
     print(f"Loading model {str(checkpoint_path or synthetic)!r} with {config.__dict__}", file=sys.stderr)
     t0 = time.perf_counter()
     model = build_model(config, quantize=quantize, device=device, checkpoint_path=checkpoint_path,
-                        max_seq_length=max_returned_tokens, prefill_rows=prompt_length, dtype=dtype)
+                        max_seq_length=max_returned_tokens, prefill_rows=prompt_length, dtype=dtype,
+                        kv_cache=kv_cache)
     print(f"Time to load the model weights: {time.perf_counter() - t0:.02f} seconds.", file=sys.stderr)
     torch.manual_seed(1234)
     eos_id = tokenizer.eos_id if tokenizer is not None else None
@@ -443,10 +456,13 @@ def _cli(argv=None) -> None:
     p.add_argument("--prompt_len", type=int, default=16)
     p.add_argument("--batch_size", type=int, default=1,
                    help="decode the samples this many at a time (1..4) through generate_batch")
+    p.add_argument("--kv_cache", default="bf16", choices=sorted(KV_CACHE_DTYPES),
+                   help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per row (0.516 x the bytes)")
     a = p.parse_args(argv)
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,
-         compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, batch_size=a.batch_size)
+         compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, batch_size=a.batch_size,
+         kv_cache=a.kv_cache)
 
 
 if __name__ == "__main__":

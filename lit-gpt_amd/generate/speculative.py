@@ -226,7 +226,8 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
          quantize: Optional[str] = "int4-g128", precision: Optional[str] = None, synthetic: Optional[str] = None,
          prompt_len: int = 16, draft: Optional[str] = None, draft_checkpoint_dir: Optional[Path] = None,
          draft_synthetic: Optional[str] = None, draft_quantize: Optional[str] = "int4-g128",
-         speculate: int = DEFAULT_SPECULATE, temperature: float = 0.0) -> None:
+         speculate: int = DEFAULT_SPECULATE, temperature: float = 0.0, kv_cache: str = "bf16") -> None:
+    """``kv_cache`` is the TARGET's cache format (generate/base.py ``--kv_cache``); a draft model keeps bf16."""
     from generate.base import build_model
 
     if (precision or "bf16-true") != "bf16-true":
@@ -259,7 +260,7 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
     print(f"Loading model {str(checkpoint_path or synthetic)!r} with {config.__dict__}", file=sys.stderr)
     t0 = time.perf_counter()
     model = build_model(config, quantize=quantize, device=device, checkpoint_path=checkpoint_path,
-                        max_seq_length=max_returned_tokens, prefill_rows=prompt_length)
+                        max_seq_length=max_returned_tokens, prefill_rows=prompt_length, kv_cache=kv_cache)
     if draft == "ngram":
         drafter = NgramDrafter()
     else:
@@ -310,6 +311,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--draft_quantize", default="int4-g128")
     p.add_argument("--speculate", type=int, default=DEFAULT_SPECULATE,
                    help=f"drafts per round (1..{GPT.MAX_WINDOW - 1})")
+    p.add_argument("--kv_cache", default="bf16", choices=["bf16", "fp8"],
+                   help="the target's KV cache format (fp8: e4m3 codes + one scale per row); a draft model keeps bf16")
     a = p.parse_args(argv)
     if sum(x is not None for x in (a.draft, a.draft_checkpoint_dir, a.draft_synthetic)) != 1:
         p.error("choose one drafter: --draft ngram, --draft_checkpoint_dir DIR or --draft_synthetic NAME")
@@ -325,7 +328,7 @@ def _cli(argv=None) -> None:
     main(a.prompt, max_new_tokens=a.max_new_tokens, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize,
          precision=a.precision, synthetic=a.synthetic, prompt_len=a.prompt_len, draft=a.draft,
          draft_checkpoint_dir=a.draft_checkpoint_dir, draft_synthetic=a.draft_synthetic,
-         draft_quantize=a.draft_quantize, speculate=a.speculate, temperature=a.temperature)
+         draft_quantize=a.draft_quantize, speculate=a.speculate, temperature=a.temperature, kv_cache=a.kv_cache)
 
 
 if __name__ == "__main__":

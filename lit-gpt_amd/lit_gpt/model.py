@@ -269,13 +269,40 @@ class GPT(nn.Module):
 
     def set_kv_cache(self, batch_size: int, rope_cache_length: Optional[int] = None,
                      device: Optional[torch.device] = None, dtype: Optional[torch.dtype] = None) -> None:
+        """``dtype=torch.float8_e4m3fn`` builds the fp8 cache (``KVCache``): e4m3 codes plus one
+        power-of-two scale per row, 132 B per row instead of 256. Every weight format takes it; what the fp8 attention
+        kernels do not cover is refused here, before any launch."""
         if rope_cache_length is None:
             rope_cache_length = self.cos.size(-1)
+        if dtype == torch.float8_e4m3fn:
+            self._kv8_check()
         for block in self.transformer.h:
             block.attn.kv_cache = block.attn.build_kv_cache(batch_size, self.max_seq_length, rope_cache_length,
                                                             device, dtype)
+        if dtype == torch.float8_e4m3fn:
+            # the cached prefill (T > 1) expands a layer's cache into this bf16 pair for the MFMA flash kernels: one
+            # pair for the model, every layer's attention is done with it before the next one fills it
+            kv0 = self.transformer.h[0].attn.kv_cache
+            scratch = tuple(torch.empty(kv0.k.shape[1:], dtype=torch.bfloat16, device=kv0.k.device) for _ in range(2))
+            for block in self.transformer.h:
+                block.attn.kv_cache.scratch = scratch
         if self.mask_cache is None or self.mask_cache.size(3) != self.max_seq_length:
             self.mask_cache = CausalMask(self.max_seq_length, device or self.transformer.wte.weight.device)
+
+    def _kv8_check(self) -> None:
+        """What the fp8 KV cache needs: the fused decode attention's geometry, bf16 activations, one device."""
+        c = self.config
+        if not ops.decode_fusable(c.head_size, c.rope_n_elem) or c.n_head // c.n_query_groups not in (1, 2, 4, 8):
+            raise NotImplementedError("an fp8 KV cache needs the fused decode attention's geometry (head_size == "
+                                      f"rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group); got head_size "
+                                      f"{c.head_size}, rope_n_elem {c.rope_n_elem}, {c.n_head} heads in "
+                                      f"{c.n_query_groups} groups")
+        if self.transformer.wte.weight.dtype == torch.float32:
+            raise NotImplementedError("an fp8 KV cache under --precision 32-true: the fp8 attention kernels take bf16 "
+                                      "activations (the fp32 path keeps an fp32 cache)")
+        if comm.get_default() is not None or any(comm.tp_hook(b.attn) is not None for b in self.transformer.h):
+            raise NotImplementedError("an fp8 KV cache under tensor parallelism: the per-rank decode step keeps the "
+                                      "bf16 cache")
 
     def clear_kv_cache(self) -> None:
         self.mask_cache = None
@@ -395,16 +422,20 @@ class CausalSelfAttention(nn.Module):
             if not isinstance(self.kv_cache, KVCache):
                 raise TypeError("You need to call `gpt.set_kv_cache()`")
             kv = self.kv_cache
-            if kv.k.dtype != qkv.dtype:  # reference KVCache.forward casts to the activation dtype (:790-791)
+            if not kv.fp8 and kv.k.dtype != qkv.dtype:  # reference KVCache.forward casts to the activation dtype (:790-791)
                 kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
             if not 0 <= kv_slot < kv.k.size(0):
                 raise ValueError(f"kv_slot {kv_slot}: the KV cache holds {kv.k.size(0)} sequence(s)")
             kc, vc = (kv.k, kv.v) if kv.k.size(0) == 1 else (kv.k[kv_slot], kv.v[kv_slot])
+            kv8 = kv.slot(kv_slot) if kv.fp8 else None
             pos = input_pos
             # callers may pass the full cos/sin tables (our GPT.forward) or rows pre-selected by input_pos (the
             # reference's GPT.forward, model.py:505-506)
             rope_pos = pos if (cos.size(0) != T or T == kc.size(-2)) else torch.arange(T, device=dev)
-        y = self._attend(qkv, kc, vc, pos, rope_pos, cos, sin)
+        if input_pos is not None and kv8 is not None:
+            y = self._attend_kv8(qkv, kv8, pos, rope_pos, cos, sin)
+        else:
+            y = self._attend(qkv, kc, vc, pos, rope_pos, cos, sin)
         out = _lin(self.proj, y.view(1, T, H * hs), residual=residual, reduce=reduce)
         return out.view(B, T, -1)
 
@@ -430,6 +461,33 @@ class CausalSelfAttention(nn.Module):
         q = ops.rope_kv_append(qkv, kc, vc, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem)
         return ops.attention(q, kc, vc, pos, H, G, hs, 1.0 / math.sqrt(hs), n_splits, workspace=ws, out=out)
 
+    def _attend_kv8(self, qkv, cache, pos, rope_pos, cos, sin, out=None) -> torch.Tensor:
+        """``_attend`` over one sequence's fp8 cache (``KVCache.slot``). Every row is scored as the cache holds it, the
+        call's own rows included. T = 1: quantizing append + attention in one launch. T > 1: the quantizing append,
+        the cache expanded into the model's bf16 scratch pair, then the bf16 prefill attention over that (no host read
+        of ``pos``: graph-safe)."""
+        c = self.config
+        H, G, hs = c.n_head, c.n_query_groups, c.head_size
+        T, dev = qkv.size(0), qkv.device
+        if qkv.dtype != torch.bfloat16:
+            raise NotImplementedError(f"an fp8 KV cache with {qkv.dtype} activations: the kernels take bf16")
+        cos = cos.to(device=dev, dtype=torch.float32).contiguous()
+        sin = sin.to(device=dev, dtype=torch.float32).contiguous()
+        scale = 1.0 / math.sqrt(hs)
+        if T == 1:
+            n_splits = ops.decode_splits(G, H // G, hs, cache[0].size(-2))
+            ws = getattr(self, "_attn_ws", None)
+            if ws is None or ws.key != (1, H, G, hs, n_splits) or ws.counters.device != dev:
+                ws = self._attn_ws = ops.AttentionWorkspace(1, H, G, hs, n_splits, dev)
+            return ops.attention_decode_fused_kv8(qkv, cache, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem, scale,
+                                                  n_splits, workspace=ws, out=out)
+        q = ops.kv8_rope_append(qkv, cache, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem)
+        kv = self.kv_cache
+        if kv.scratch is None or kv.scratch[0].shape != cache[0].shape or kv.scratch[0].device != dev:
+            kv.scratch = tuple(torch.empty(cache[0].shape, dtype=torch.bfloat16, device=dev) for _ in range(2))
+        kd, vd = ops.kv8_dequantize(cache, out=kv.scratch)
+        return ops.attention(q, kd, vd, pos, H, G, hs, scale, 1, out=out)
+
     def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, *,
                     norm: "RMSNorm", residual: torch.Tensor) -> torch.Tensor:
         """Batched decode step: x (B, C), one token of each of B sequences at ``pos`` (B,). The qkv and the
@@ -440,12 +498,15 @@ class CausalSelfAttention(nn.Module):
         B = x.size(0)
         kv = self.kv_cache
         qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
-        if kv.k.dtype != qkv.dtype:
+        if not kv.fp8 and kv.k.dtype != qkv.dtype:
             kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
         y = torch.empty(B, c.n_head * c.head_size, dtype=qkv.dtype, device=qkv.device)
         for b in range(B):
             p = pos[b:b + 1]
-            self._attend(qkv[b:b + 1], kv.k[b], kv.v[b], p, p, cos, sin, out=y[b:b + 1])
+            if kv.fp8:
+                self._attend_kv8(qkv[b:b + 1], kv.slot(b), p, p, cos, sin, out=y[b:b + 1])
+            else:
+                self._attend(qkv[b:b + 1], kv.k[b], kv.v[b], p, p, cos, sin, out=y[b:b + 1])
         return _lin(self.proj, y, residual=residual, rows=True)
 
     def decode_window(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor, *,
@@ -459,7 +520,7 @@ class CausalSelfAttention(nn.Module):
         M, dev = x.size(0), x.device
         kv = self.kv_cache
         qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
-        if kv.k.dtype != qkv.dtype:
+        if not kv.fp8 and kv.k.dtype != qkv.dtype:
             kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
         kc, vc = kv.k[0], kv.v[0]
         n_splits = ops.decode_splits(G, H // G, hs, kc.size(-2))
@@ -469,8 +530,12 @@ class CausalSelfAttention(nn.Module):
             ws = wss[M] = ops.AttentionWorkspace(M, H, G, hs, n_splits, dev)
         cos = cos.to(device=dev, dtype=torch.float32).contiguous()
         sin = sin.to(device=dev, dtype=torch.float32).contiguous()
-        y = ops.attention_decode_window(qkv, kc, vc, pos0, cos, sin, H, G, hs, c.rope_n_elem, 1.0 / math.sqrt(hs),
-                                        n_splits, workspace=ws)
+        if kv.fp8:
+            y = ops.attention_decode_window_kv8(qkv, kv.slot(0), pos0, cos, sin, H, G, hs, c.rope_n_elem,
+                                                1.0 / math.sqrt(hs), n_splits, workspace=ws)
+        else:
+            y = ops.attention_decode_window(qkv, kc, vc, pos0, cos, sin, H, G, hs, c.rope_n_elem,
+                                            1.0 / math.sqrt(hs), n_splits, workspace=ws)
         return _lin(self.proj, y, residual=residual, rows=True)
 
     def scaled_dot_product_attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -693,14 +758,52 @@ class LayerNorm(nn.LayerNorm):
 
 
 class KVCache(nn.Module):
+    """``k`` / ``v`` (B, G, S, hs) in ``dtype``, or the fp8 form for ``dtype=torch.float8_e4m3fn``:
+    ``k`` / ``v`` hold OCP e4m3 codes as uint8 (no torch fp8 operator runs on the device) and ``k_scale`` / ``v_scale``
+    (B, G, S) fp32 one power-of-two scale per row — 132 B per row of 128 instead of 256. ``cache_dtype`` names the
+    format (``k.dtype`` is uint8 for an fp8 cache)."""
+
     def __init__(self, k_shape: Tuple[int, int, int, int], v_shape: Tuple[int, int, int, int],
                  device: Optional[torch.device] = None, dtype: Optional[torch.dtype] = None) -> None:
         super().__init__()
+        self.cache_dtype = dtype if dtype is not None else torch.get_default_dtype()
+        self.scratch = None  # fp8: the bf16 (G, S, hs) pair of the cached prefill (GPT.set_kv_cache shares one)
+        if self.fp8:
+            if tuple(k_shape) != tuple(v_shape):
+                raise NotImplementedError("an fp8 KV cache holds full-rotary keys: k and v rows of one size")
+            self.register_buffer("k", torch.zeros(k_shape, device=device, dtype=torch.uint8), persistent=False)
+            self.register_buffer("v", torch.zeros(v_shape, device=device, dtype=torch.uint8), persistent=False)
+            self.register_buffer("k_scale", torch.ones(k_shape[:3], device=device, dtype=torch.float32),
+                                 persistent=False)
+            self.register_buffer("v_scale", torch.ones(v_shape[:3], device=device, dtype=torch.float32),
+                                 persistent=False)
+            return
         self.register_buffer("k", torch.zeros(k_shape, device=device, dtype=dtype), persistent=False)
         self.register_buffer("v", torch.zeros(v_shape, device=device, dtype=dtype), persistent=False)
 
+    @property
+    def fp8(self) -> bool:
+        return self.cache_dtype == torch.float8_e4m3fn
+
+    def slot(self, b: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """One sequence of an fp8 cache as the ops take it: (k codes, v codes, k scales, v scales)."""
+        return self.k[b], self.v[b], self.k_scale[b], self.v_scale[b]
+
+    def dequantized(self, slot: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """bf16 (k, v), each (G, S, hs), of one sequence of an fp8 cache: float(code) * scale, exact (tests, debugging)."""
+        if not self.fp8:
+            raise TypeError("dequantized() reads an fp8 KV cache")
+        if self.k.is_cuda:
+            return ops.kv8_dequantize(self.slot(slot))
+        kc, vc, ks, vs = self.slot(slot)
+        return tuple((c.view(torch.float8_e4m3fn).float() * s.unsqueeze(-1)).to(torch.bfloat16)
+                     for c, s in ((kc, ks), (vc, vs)))
+
     def forward(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference API (model.py:788-795); the fused path writes the cache inside ``lga_rope_kv_append``."""
+        if self.fp8:
+            raise NotImplementedError("an fp8 KV cache is written by the quantizing kernels (ops.kv8_rope_append, "
+                                      "ops.attention_decode_fused_kv8), not through the reference's index_copy_")
         self.k = self.k.to(k.dtype)
         self.v = self.v.to(v.dtype)
         return self.k.index_copy_(2, input_pos, k), self.v.index_copy_(2, input_pos, v)
@@ -708,6 +811,9 @@ class KVCache(nn.Module):
     def reset_parameters(self) -> None:
         torch.nn.init.zeros_(self.k)
         torch.nn.init.zeros_(self.v)
+        if self.fp8:
+            torch.nn.init.ones_(self.k_scale)
+            torch.nn.init.ones_(self.v_scale)
 
 
 def build_rope_cache(seq_len: int, n_elem: int, device: Optional[torch.device] = None, base: int = 10000,

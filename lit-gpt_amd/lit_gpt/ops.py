@@ -75,6 +75,12 @@ SIGNATURES = {
     "lga_attention_workspace_bytes": [_I, _I, _I, _I],
     "lga_attention_decode_fused": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "lga_attention_decode_window": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    "lga_attention_decode_fused_kv8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F,
+                                       _P],
+    "lga_attention_decode_window_kv8": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F,
+                                        _P],
+    "lga_kv8_rope_append": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "lga_kv8_dequantize": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_spec_accept": [_P, _I, _I, _P, _P, _P, _P, _P],
     "lga_argmax": [_P, _I, _P, _P, _P, _P],
     "lga_q4_gemv_argmax_work_bytes": [_I, _I],
@@ -674,6 +680,103 @@ def attention_decode_window(qkv, k_cache, v_cache, pos0, cos, sin, n_head, n_que
         _dev(v_cache, "v_cache", torch.bfloat16), _dev(pos0, "pos0", torch.int64), _dev(cos, "cos", torch.float32),
         _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, M, n_head,
         n_query_groups, head_size, rope_n_elem, max_seq, n_splits, float(scale), _stream()))
+    return y
+
+
+# ------------------------------------------------------------------------------------------ fp8 (e4m3) KV cache
+# One sequence's cache is (k_codes, v_codes, k_scale, v_scale): codes (G, max_seq, 128) uint8, scales (G, max_seq)
+# fp32 powers of two (include/litgpt_amd.h states the format). The four wrappers mirror their bf16 twins.
+def _kv8(cache, name):
+    kc, vc, ks, vs = cache
+    if kc.shape != vc.shape or kc.dim() != 3 or kc.shape[-1] != 128 or ks.shape != kc.shape[:2] or vs.shape != ks.shape:
+        raise ValueError(f"{name}: an fp8 cache is codes (G, max_seq, 128) uint8 x 2 and scales (G, max_seq) fp32 x 2, "
+                         f"got {tuple(kc.shape)}, {tuple(vc.shape)}, {tuple(ks.shape)}, {tuple(vs.shape)}")
+    return (_dev(kc, "k_codes", torch.uint8), _dev(vc, "v_codes", torch.uint8), _dev(ks, "k_scale", torch.float32),
+            _dev(vs, "v_scale", torch.float32))
+
+
+def kv8_rope_append(qkv, cache, cache_pos, rope_pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem,
+                    q_out=None):
+    """``rope_kv_append`` into an fp8 cache: q (T, H, hs) roped; k (roped) and v quantized row by row into the codes
+    and scales at rows cache_pos."""
+    T = qkv.shape[0]
+    ptrs = _kv8(cache, "kv8_rope_append")
+    q = q_out if q_out is not None else torch.empty(T, n_head, head_size, dtype=torch.bfloat16, device=qkv.device)
+    _check(load_library().lga_kv8_rope_append(
+        _dev(qkv, "qkv", torch.bfloat16), _dev(q, "q", torch.bfloat16), *ptrs,
+        _dev(cache_pos, "cache_pos", torch.int64), _dev(rope_pos, "rope_pos", torch.int64),
+        _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32), cos.shape[0], T, n_head, n_query_groups,
+        head_size, rope_n_elem, cache[0].shape[-2], _stream()))
+    return q
+
+
+def kv8_dequantize(cache, n=None, out=None):
+    """Rows [0, n) (default: all) of an fp8 cache as bf16 (k, v), each (G, n, 128): float(code) * scale, exact."""
+    ptrs = _kv8(cache, "kv8_dequantize")
+    G, S, hs = cache[0].shape
+    n = S if n is None else n
+    if out is None:
+        out = (torch.empty(G, n, hs, dtype=torch.bfloat16, device=cache[0].device),
+               torch.empty(G, n, hs, dtype=torch.bfloat16, device=cache[0].device))
+    if out[0].numel() != G * n * hs or out[1].numel() != G * n * hs:
+        raise ValueError("kv8_dequantize: out must hold two (G, n, 128) bf16 buffers")
+    _check(load_library().lga_kv8_dequantize(*ptrs, _dev(out[0], "k_out", torch.bfloat16),
+                                             _dev(out[1], "v_out", torch.bfloat16), G, n, hs, S, _stream()))
+    return out
+
+
+def attention_decode_fused_kv8(qkv, cache, cache_pos, rope_pos, cos, sin, n_head, n_query_groups, head_size,
+                               rope_n_elem, scale, n_splits=1, workspace: Optional[AttentionWorkspace] = None,
+                               out=None):
+    """``attention_decode_fused`` over an fp8 cache: the new row is quantized into the cache at cache_pos[0] and every
+    key and value, the new one included, is read as the cache holds it."""
+    if qkv.shape[0] != 1:
+        raise ValueError("attention_decode_fused_kv8 handles exactly one token (T = 1)")
+    ptrs = _kv8(cache, "attention_decode_fused_kv8")
+    y = out if out is not None else torch.empty(1, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
+    if n_splits > 1:
+        if workspace is None or workspace.key != (1, n_head, n_query_groups, head_size, n_splits):
+            workspace = AttentionWorkspace(1, n_head, n_query_groups, head_size, n_splits, qkv.device)
+        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
+    else:
+        ws = cnt = None
+    _check(load_library().lga_attention_decode_fused_kv8(
+        _dev(qkv, "qkv", torch.bfloat16), *ptrs, _dev(cache_pos, "cache_pos", torch.int64),
+        _dev(rope_pos, "rope_pos", torch.int64), _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32),
+        cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, n_head, n_query_groups, head_size, rope_n_elem,
+        cache[0].shape[-2], n_splits, float(scale), _stream()))
+    return y
+
+
+def attention_decode_window_kv8(qkv, cache, pos0, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale,
+                                n_splits=1, workspace: Optional[AttentionWorkspace] = None, out=None):
+    """``attention_decode_window`` over an fp8 cache: y (M, H*hs), codes and scales bit-identical to M successive
+    ``attention_decode_fused_kv8`` calls with the same ``n_splits``."""
+    M = qkv.shape[0]
+    if qkv.dim() != 2 or not 1 <= M <= MAX_WINDOW_ROWS:
+        raise ValueError(f"attention_decode_window_kv8: qkv must be (M, (H + 2G) * hs) with 1 <= M <= "
+                         f"{MAX_WINDOW_ROWS}, got {tuple(qkv.shape)}")
+    if qkv.shape[1] != (n_head + 2 * n_query_groups) * head_size:
+        raise ValueError("attention_decode_window_kv8: qkv rows must hold (H + 2G) * hs values")
+    if pos0.numel() != 1:
+        raise ValueError("attention_decode_window_kv8: pos0 holds one position (row r sits at pos0 + r)")
+    ptrs = _kv8(cache, "attention_decode_window_kv8")
+    y = out if out is not None else torch.empty(M, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
+    if y.numel() != M * n_head * head_size:
+        raise ValueError("attention_decode_window_kv8: out must hold (M, H * hs) values")
+    if n_splits > 1:
+        if workspace is None:
+            raise ValueError("attention_decode_window_kv8: split attention needs an AttentionWorkspace(M, ...)")
+        if workspace.key != (M, n_head, n_query_groups, head_size, n_splits):
+            raise ValueError(f"attention_decode_window_kv8: workspace built for {workspace.key}, the call needs "
+                             f"{(M, n_head, n_query_groups, head_size, n_splits)}")
+        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
+    else:
+        ws = cnt = None
+    _check(load_library().lga_attention_decode_window_kv8(
+        _dev(qkv, "qkv", torch.bfloat16), *ptrs, _dev(pos0, "pos0", torch.int64), _dev(cos, "cos", torch.float32),
+        _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, M, n_head,
+        n_query_groups, head_size, rope_n_elem, cache[0].shape[-2], n_splits, float(scale), _stream()))
     return y
 
 

@@ -85,10 +85,12 @@ def _plan(model, tokens, n_scored: int) -> Tuple[torch.Tensor, int]:
     return ids, T
 
 
-def _hidden(model, ids: torch.Tensor, T: int, n_scored: int) -> torch.Tensor:
-    """The last ``n_scored`` rows of the last block's output for the input ``ids[:-1]`` (no KV cache involved)."""
+def _hidden(model, ids: torch.Tensor, T: int, n_scored: int, cached: bool = False) -> torch.Tensor:
+    """The last ``n_scored`` rows of the last block's output for the input ``ids[:-1]``: the no-cache causal forward,
+    or with ``cached`` a prefill through the model's KV cache at positions 0 .. T - 1 (which it overwrites)."""
     dev = model.transformer.wte.weight.device
-    x = model(ids[:-1].to(dev).view(1, -1), input_pos=None, hidden_only=True)
+    pos = torch.arange(T, device=dev) if cached else None
+    x = model(ids[:-1].to(dev).view(1, -1), input_pos=pos, hidden_only=True)
     return x.view(T, -1)[T - n_scored:]
 
 
@@ -108,12 +110,14 @@ def _head(model, h: torch.Tensor) -> torch.Tensor:
 
 
 @torch.inference_mode()
-def score_tokens(model, tokens, n_scored: int, *, return_hidden: bool = False):
+def score_tokens(model, tokens, n_scored: int, *, return_hidden: bool = False, cached: bool = False):
     """``(logprobs fp32 (n_scored,), greedy int32 (n_scored,))`` on the model's device: for the last ``n_scored``
     tokens of ``tokens``, the log-probability the model gives each one after the tokens before it, and the model's
     own arg-max at that position. ``tokens[:-1]`` is the input (at most ``model.max_seq_length`` long).
     ``return_hidden`` appends the ``(n_scored, n_embd)`` hidden rows the head ran on, which ``compare_tokens`` takes
-    as ``hidden_q`` so that a caller wanting both runs this model's blocks once."""
+    as ``hidden_q`` so that a caller wanting both runs this model's blocks once. ``cached`` scores the window as a
+    prefill through the model's KV cache (``input_pos = arange(T)``) instead of the no-cache forward, so the
+    log-probabilities reflect the cache format — an fp8 cache's quantized K / V (eval/perplexity.py ``--kv_cache``)."""
     from lit_gpt import ops
 
     ids, T = _plan(model, tokens, n_scored)
@@ -122,7 +126,7 @@ def score_tokens(model, tokens, n_scored: int, *, return_hidden: bool = False):
     greedy = torch.empty(n_scored, dtype=torch.int32, device=dev)
     h = None
     if n_scored:
-        h = _hidden(model, ids, T, n_scored)
+        h = _hidden(model, ids, T, n_scored, cached)
         targets = ids[ids.numel() - n_scored:].to(device=dev, dtype=torch.int32)
         for a in range(0, n_scored, HEAD_ROWS):
             b = min(n_scored, a + HEAD_ROWS)
