@@ -402,6 +402,17 @@ int lga_sample_topk(const void* logits, int n, int top_k, float temperature, con
                     unsigned long long seed, unsigned long long* counter, int64_t* out_idx, int32_t* token_out,
                     int64_t* pos_inout, const void* table, int n_embd, int vocab, void* emb_out, int32_t* kept_out,
                     void* probs_out, lga_stream_t stream);
+/* Speculative acceptance under top-k sampling: lga_spec_accept with each row's argmax replaced by lga_sample_topk's
+ * draw. logits (M, n) bf16 contiguous (rows need no alignment), window (M) int32 as in lga_spec_accept. t_r = the
+ * token lga_sample_topk draws from row r at top_k / temperature under uniform[r] (uniform: M fp32), or, with uniform
+ * NULL, under the uniform of draw number *counter + r. a = the largest a <= M - 1 with window[r + 1] == t_r for all
+ * r < a. out (M + 1) int32 = [a, t_0..t_a, -1...], *token_inout = t_a (may be &window[0]), *pos_inout += a + 1
+ * (either may be NULL), and on the counter path *counter += a + 1. Two launches: one workgroup per row writes
+ * sampled (8 int32 of scratch), then one small launch does the rest. 1 <= M <= 8, n <= 65536, top_k 1..1024. */
+int lga_spec_accept_sample(const void* logits, int M, int n, int top_k, float temperature, const float* uniform,
+                           unsigned long long seed, unsigned long long* counter, const int32_t* window,
+                           int32_t* sampled, int32_t* out, int32_t* token_inout, int64_t* pos_inout,
+                           lga_stream_t stream);
 
 /* -- fp32 forward (the reference's --precision 32-true, generate/base.py:132; BASELINE config 1 pythia-160m fp32):
  *    float32 weights and activations, no bf16 rounding; plumbing-sized kernels (csrc/fp32.hip) -------------- */

@@ -258,15 +258,22 @@ __device__ __forceinline__ unsigned wave_incl_scan(unsigned v, int lane) {
   return v;
 }
 
-// One workgroup of 1024 threads; thread t owns logits [t EPT, t EPT + EPT) (index order = thread order, so every
-// "in index order" below is a block prefix sum). The logits are staged once in LDS (coalesced), padded with -inf
-// (pads sit after every real index, so a tie rule that takes the lowest indices never reaches them: k <= n).
+// the uniform of draw number `cn` under `seed`: exact in fp32, in (0, 1) (lit_gpt/ops.py sampler_uniform is its host
+// twin)
+__device__ __forceinline__ float draw_uniform(unsigned long long seed, unsigned long long cn) {
+  return ((float)(mix64(seed ^ (cn * 0xD1B54A32D192ED03ull)) >> 41) + 0.5f) * 0x1.0p-23f;
+}
+
+// The sampler of one row, shared by the one-row kernel and the speculative window kernel below (so the two draw the
+// same token from the same logits and uniform by construction). One workgroup of 1024 threads; thread t owns logits
+// [t EPT, t EPT + EPT) (index order = thread order, so every "in index order" below is a block prefix sum). The logits
+// are staged once in LDS (coalesced), padded with -inf (pads sit after every real index, so a tie rule that takes the
+// lowest indices never reaches them: k <= n). `u0` is the draw's uniform (thread 0's copy is the one used). Returns
+// the drawn token to every thread, after a workgroup barrier.
 template <int EPT>
-__global__ void __launch_bounds__(1024) topk_sample_kernel(
-    const uint16_t* __restrict__ logits, int n, int k, float temperature, const float* __restrict__ uniform,
-    unsigned long long seed, unsigned long long* __restrict__ counter, int64_t* __restrict__ out_idx,
-    int32_t* __restrict__ token_out, int64_t* __restrict__ pos_inout, const uint16_t* __restrict__ table, int C,
-    int V, uint16_t* __restrict__ emb_out, int32_t* __restrict__ kept_out, uint16_t* __restrict__ probs_out) {
+__device__ __forceinline__ int topk_sample_row(const uint16_t* __restrict__ logits, int n, int k, float temperature,
+                                               float u0, int32_t* __restrict__ kept_out,
+                                               uint16_t* __restrict__ probs_out) {
   constexpr int NT = 1024, NW = 16;
   static_assert(EPT % 8 == 0, "16-B LDS reads");
   __shared__ __attribute__((aligned(16))) uint16_t sx[NT * EPT];
@@ -281,16 +288,6 @@ __global__ void __launch_bounds__(1024) topk_sample_kernel(
   __shared__ int s_tok;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   k = min(k, n);
-  float u0 = 0.0f;  // thread 0: the draw's uniform, fetched now so its global round trip overlaps the selection
-  if (t == 0) {
-    if (uniform) {
-      u0 = *uniform;
-    } else {
-      const unsigned long long cn = *counter;
-      *counter = cn + 1;
-      u0 = ((float)(mix64(seed ^ (cn * 0xD1B54A32D192ED03ull)) >> 41) + 0.5f) * 0x1.0p-23f;  // exact, in (0, 1)
-    }
-  }
   // stage the logits (pairs of bf16 per load when the row is 4-B aligned), -inf past n; clear the first histogram
   if (((uintptr_t)logits & 3) == 0) {
     for (int i2 = t; i2 < NT * EPT / 2; i2 += NT) {
@@ -487,7 +484,28 @@ __global__ void __launch_bounds__(1024) topk_sample_kernel(
   }
   __syncthreads();
   LGA_STRACE(5);
-  const int pick = s_tok;
+  return s_tok;
+}
+
+template <int EPT>
+__global__ void __launch_bounds__(1024) topk_sample_kernel(
+    const uint16_t* __restrict__ logits, int n, int k, float temperature, const float* __restrict__ uniform,
+    unsigned long long seed, unsigned long long* __restrict__ counter, int64_t* __restrict__ out_idx,
+    int32_t* __restrict__ token_out, int64_t* __restrict__ pos_inout, const uint16_t* __restrict__ table, int C,
+    int V, uint16_t* __restrict__ emb_out, int32_t* __restrict__ kept_out, uint16_t* __restrict__ probs_out) {
+  constexpr int NT = 1024;
+  const int t = threadIdx.x;
+  float u0 = 0.0f;  // thread 0: the draw's uniform, fetched now so its global round trip overlaps the selection
+  if (t == 0) {
+    if (uniform) {
+      u0 = *uniform;
+    } else {
+      const unsigned long long cn = *counter;
+      *counter = cn + 1;
+      u0 = draw_uniform(seed, cn);
+    }
+  }
+  const int pick = topk_sample_row<EPT>(logits, n, k, temperature, u0, kept_out, probs_out);
   if (t == 0) {
     if (out_idx) *out_idx = pick;
     if (token_out) *token_out = pick;
@@ -500,12 +518,52 @@ __global__ void __launch_bounds__(1024) topk_sample_kernel(
   }
 }
 
+// ---- speculative decoding under top-k sampling: the verify window's samples, then the accepted prefix ------------
+// logits (M, n) are the target's rows for window[0..M-1] as in spec_accept_kernel. Row r is sampled by workgroup r
+// with topk_sample_row — the one-row sampler's token for that row's logits — under uniform[r], or the uniform of
+// draw number *counter + r: the draw `generate` spends on the token at that position when every earlier draft of
+// the window is accepted (and a later row's token is only used in that case). The row workgroups read the counter
+// and write sampled[r] only.
+template <int EPT>
+__global__ void __launch_bounds__(1024) window_sample_kernel(const uint16_t* __restrict__ logits, int n, int k,
+                                                             float temperature, const float* __restrict__ uniform,
+                                                             unsigned long long seed,
+                                                             const unsigned long long* __restrict__ counter,
+                                                             int32_t* __restrict__ sampled) {
+  const int r = blockIdx.x;
+  float u0 = 0.0f;
+  if (threadIdx.x == 0) u0 = uniform ? uniform[r] : draw_uniform(seed, *counter + (unsigned long long)r);
+  // (a row starts at any 2-B boundary when n is odd: topk_sample_row picks its load form from the row's pointer)
+  const int pick = topk_sample_row<EPT>(logits + (size_t)r * n, n, k, temperature, u0, nullptr, nullptr);
+  if (threadIdx.x == 0) sampled[r] = pick;
+}
+
+// The second launch (the launch boundary orders it after every row's sampled[r]): a = the largest a <= M - 1 with
+// window[r + 1] == sampled[r] for every r < a; out = [a, t_0 .. t_a, -1 ...], *token_inout = t_a, *pos_inout += a + 1
+// and, on the counter path, *counter += a + 1: the draws of the emitted tokens are spent, the rest are drawn again.
+__global__ void __launch_bounds__(64) window_sample_accept_kernel(const int32_t* __restrict__ sampled, int M,
+                                                                  const int32_t* window, int32_t* __restrict__ out,
+                                                                  int32_t* token_inout,  // (may be &window[0])
+                                                                  int64_t* __restrict__ pos_inout,
+                                                                  unsigned long long* __restrict__ counter) {
+  if (threadIdx.x != 0) return;
+  int a = 0;
+  while (a < M - 1 && window[a + 1] == sampled[a]) ++a;
+  out[0] = a;
+  for (int r = 0; r < M; ++r) out[1 + r] = r <= a ? sampled[r] : -1;
+  if (token_inout) *token_inout = sampled[a];
+  if (pos_inout) *pos_inout += a + 1;
+  if (counter) *counter += (unsigned long long)(a + 1);
+}
+
 }  // namespace lga
 
 int lga::preload_sample() {
   return lga::preload(lga::argmax_kernel<true>) + lga::preload(lga::argmax_kernel<false>) +
          lga::preload(lga::topk_sample_kernel<16>) + lga::preload(lga::topk_sample_kernel<32>) +
-         lga::preload(lga::topk_sample_kernel<64>);
+         lga::preload(lga::topk_sample_kernel<64>) + lga::preload(lga::window_sample_kernel<16>) +
+         lga::preload(lga::window_sample_kernel<32>) + lga::preload(lga::window_sample_kernel<64>) +
+         lga::preload(lga::window_sample_accept_kernel);
 }
 
 extern "C" int lga_argmax(const void* logits, int n, int64_t* out_idx, int32_t* token_out, int64_t* pos_inout,
@@ -572,6 +630,29 @@ extern "C" int lga_sample_topk(const void* logits, int n, int top_k, float tempe
   else if (n <= 1024 * 32) LGA_TOPK(32);
   else LGA_TOPK(64);
 #undef LGA_TOPK
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_spec_accept_sample(const void* logits, int M, int n, int top_k, float temperature,
+                                      const float* uniform, unsigned long long seed, unsigned long long* counter,
+                                      const int32_t* window, int32_t* sampled, int32_t* out, int32_t* token_inout,
+                                      int64_t* pos_inout, hipStream_t stream) {
+  LGA_CHECK_ARG(logits && window && out && sampled, "lga_spec_accept_sample: bad arguments");
+  LGA_CHECK_ARG(M >= 1 && M <= lga::kMaxWindow, "lga_spec_accept_sample: M must be in [1, 8]");
+  LGA_CHECK_ARG(n > 0 && n <= 1024 * 64, "lga_spec_accept_sample: needs 0 < n <= 65536 logits per row");
+  LGA_CHECK_ARG(top_k >= 1 && top_k <= lga::kMaxTopK, "lga_spec_accept_sample: top_k must be in [1, 1024]");
+  LGA_CHECK_ARG(temperature > 0.0f, "lga_spec_accept_sample: temperature must be > 0 (0 is lga_spec_accept)");
+  LGA_CHECK_ARG(uniform || counter, "lga_spec_accept_sample: needs uniforms or an RNG counter");
+#define LGA_WINDOW_TOPK(EPT)                                                                                      \
+  lga::window_sample_kernel<EPT><<<M, 1024, 0, stream>>>((const uint16_t*)logits, n, top_k, temperature, uniform, \
+                                                         seed, counter, sampled)
+  if (n <= 1024 * 16) LGA_WINDOW_TOPK(16);
+  else if (n <= 1024 * 32) LGA_WINDOW_TOPK(32);
+  else LGA_WINDOW_TOPK(64);
+#undef LGA_WINDOW_TOPK
+  // with explicit uniforms the counter is left alone, as lga_sample_topk leaves it
+  lga::window_sample_accept_kernel<<<1, 64, 0, stream>>>(sampled, M, window, out, token_inout, pos_inout,
+                                                         uniform ? nullptr : counter);
   LGA_LAUNCH_RETURN();
 }
 

@@ -1,11 +1,13 @@
-"""Greedy speculative decoding on the MI355X: a drafter proposes up to ``speculate`` tokens, the target model scores
-them as ONE verify window (``GPT.decode_window``: every weight streamed once for the window's rows, one window
-attention launch per block), and the longest prefix the target agrees with is kept, plus the target's own next token.
+"""Speculative decoding on the MI355X, greedy or under top-k sampling: a drafter proposes up to ``speculate``
+tokens, the target model scores them as ONE verify window (``GPT.decode_window``: every weight streamed once for the
+window's rows, one window attention launch per block), and the longest prefix the target agrees with is kept, plus
+the target's own next token.
 
 The promise: **speculation never changes the result.** Row r of the verify window has the bits of the one-row decode
 step at that position (the rows GEMVs and ``lga_attention_decode_window`` are bit-identical to their one-row
-launches), so ``generate_speculative`` returns exactly the tokens ``generate(..., temperature=0)`` returns, whatever
-the drafter proposes. Two things this rests on:
+launches), so ``generate_speculative`` returns exactly the tokens ``generate`` returns, whatever the drafter
+proposes: at temperature 0 the arg-maxes, and at ``temperature > 0`` with ``top_k`` the tokens ``generate`` samples
+with the same seed. Two things this rests on:
 
   * the same ``max_seq_length``: ``ops.decode_splits`` derives the attention split count from the cache length and
     the bits of the attention output depend on it, so the run uses the cache ``generate`` would use — it is never
@@ -13,7 +15,13 @@ the drafter proposes. Two things this rests on:
   * stale cache rows: rejected rows leave K/V past the accepted position. Decode attention reads no row past its own
     position and the next window overwrites them, so no rollback copy is made.
 
-Greedy only: speculative *sampling* (temperature > 0) is a different algorithm and raises ``NotImplementedError``.
+Sampling (``temperature > 0`` with ``top_k`` in 1..1024, the device sampler of ``generate``): that sampler's uniform
+for draw number n is a pure function of (seed, n), so the n-th generated token is a function of (the target's logits
+at its position, seed, n). The verify window samples row r with draw number c + r, c the tokens generated so far
+(``lga_spec_accept_sample``), and accepts draft r iff it EQUALS that sample: every emitted token is the one
+``generate`` draws, and the drafts only decide how many a round yields. This is not rejection sampling (which has
+the right distribution but does not reproduce ``generate``). Without ``top_k`` the run is greedy only: sampling at
+temperature > 0 raises ``NotImplementedError``.
 """
 
 from __future__ import annotations
@@ -91,13 +99,25 @@ class ModelDrafter:
     proposes by one-row greedy steps whose tokens stay on the device, and before each round is re-pointed
     (``DecodeGraph.reset``) at the accepted prefix. Its cache holds the K/V of positions below ``valid``; after a fully
     accepted round the last draft token's K/V is missing (that token was proposed, never run), so ``propose`` first
-    runs the missing positions, then drafts."""
+    runs the missing positions, then drafts.
 
-    def __init__(self, draft_model: GPT) -> None:
+    Under sampling (``set_sampling``) with ``coupled=True`` the draft model proposes by sampling its OWN logits with
+    the TARGET's uniforms: draft i of a round that starts with n tokens generated uses draw number n + i of the
+    target's seed, at the target's temperature and top_k (its ``DecodeGraph`` samples with a counter of its own, set
+    to n before the step that produces draft 0). The target accepts a draft iff it equals its own sample under that
+    same uniform, so a coupled draft is accepted whenever both inverse CDFs land on the same token — with probability
+    approaching 1 as the draft's distribution approaches the target's — while a greedy draft is accepted with at most
+    the target's largest probability. ``coupled=False`` keeps greedy drafting under sampling."""
+
+    def __init__(self, draft_model: GPT, coupled: bool = True) -> None:
         self.model = draft_model
+        self.coupled = coupled
         self.dg = None
         self.valid = 0
         self.buf: Optional[torch.Tensor] = None
+        self.sampling = None  # (temperature, top_k, seed) while drafting with the target's uniforms
+        self.rng = None
+        self.T = 0
 
     def check(self, target: GPT) -> None:
         if self.model.config.padded_vocab_size != target.config.padded_vocab_size:
@@ -106,23 +126,36 @@ class ModelDrafter:
         if self.model.transformer.wte.weight.device != target.transformer.wte.weight.device:
             raise ValueError("the draft model must sit on the target's device")
 
+    def set_sampling(self, temperature: float, top_k: Optional[int], seed: int) -> None:
+        """The target's sampling setting for the run about to ``begin`` (temperature 0: greedy)."""
+        self.sampling = (float(temperature), int(top_k), int(seed)) if temperature > 0.0 and self.coupled else None
+
     def begin(self, prompt: torch.Tensor, first_token: int) -> None:
         m = self.model
         T = prompt.size(0)
         if m.max_seq_length < T + 1:
             raise NotImplementedError(f"draft model max_seq_length {m.max_seq_length} is shorter than the prompt")
         m(prompt.view(1, -1), torch.arange(0, T, device=prompt.device), last_token_only=True)  # fills its cache
-        self.valid = T
+        self.valid = self.T = T
         self.dg = None
         self.buf = torch.zeros(GPT.MAX_WINDOW, dtype=torch.int32, device=prompt.device)
+        self.rng = None
+        if self.sampling is not None:
+            from generate.base import SamplerRNG
+
+            self.rng = SamplerRNG(prompt.device, seed=self.sampling[2])
 
     def _run(self, token: int, pos: int) -> None:
-        """One draft step of ``token`` at ``pos``; its greedy successor is left in ``dg.token``."""
+        """One draft step of ``token`` at ``pos``; its successor (greedy, or sampled with the draw number in
+        ``rng.counter``, which the step advances) is left in ``dg.token``."""
         if self.dg is None:
             from lit_gpt.runtime import DecodeGraph
 
             first = torch.tensor([token], dtype=torch.int32, device=self.buf.device)
-            self.dg = DecodeGraph(self.model, first, pos)  # runs that step itself, then captures
+            kw = {}
+            if self.rng is not None:
+                kw = dict(temperature=self.sampling[0], top_k=self.sampling[1], rng=self.rng)
+            self.dg = DecodeGraph(self.model, first, pos, **kw)  # runs that step itself, then captures
         else:
             self.dg.reset(token, pos)
             self.dg.step()
@@ -136,6 +169,8 @@ class ModelDrafter:
         while self.valid < P:  # catch up (after a fully accepted round: the last draft token's position)
             self._run(int(tokens[self.valid]), self.valid)
             self.valid += 1
+        if self.rng is not None:  # draft 0 is generated token number len(tokens) - T (the catch-up steps drew too)
+            self.rng.counter.fill_(len(tokens) - self.T)
         self._run(int(tokens[P]), P)
         self.buf[0:1].copy_(self.dg.token.view(-1))
         for i in range(1, k):
@@ -180,17 +215,28 @@ def speculative_rounds(executor, drafter, tokens: List[int], n_steps: int, max_s
 @torch.inference_mode()
 def generate_speculative(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, drafter, *,
                          speculate: int = DEFAULT_SPECULATE, eos_id: Optional[int] = None, use_graph: bool = True,
-                         stats: Optional[Dict[str, int]] = None, temperature: float = 0.0) -> torch.Tensor:
+                         stats: Optional[Dict[str, int]] = None, temperature: float = 0.0,
+                         top_k: Optional[int] = None, rng=None) -> torch.Tensor:
     """``generate(model, prompt, max_returned_tokens, temperature=0.0, eos_id=eos_id)``, token for token, in fewer
     target passes: each round verifies up to ``speculate`` drafts of ``drafter`` (``NgramDrafter``, ``ModelDrafter``)
     in one window and emits the accepted ones plus the target's next token. The KV cache must be the one ``generate``
     would run with (same ``max_seq_length``: see the module docstring). One device -> host read per round.
-    ``stats`` collects ``rounds`` (target passes), ``proposed``, ``accepted`` and ``tokens``."""
-    from generate.base import next_token
+    ``stats`` collects ``rounds`` (target passes), ``proposed``, ``accepted`` and ``tokens``.
 
-    if temperature > 0.0:
-        raise NotImplementedError("generate_speculative is greedy only: speculative sampling (temperature > 0) is a "
-                                  "different algorithm")
+    With ``temperature > 0`` and ``top_k`` in 1..1024 it returns, token for token, what ``generate(model, prompt,
+    max_returned_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id, rng=SamplerRNG(device, seed=s))``
+    returns for the seed ``s`` of ``rng`` (a ``generate.base.SamplerRNG``; omitted: seeded from torch's generator, as
+    ``generate`` does). The prefill's token is draw 0 and the n-th generated token draw n."""
+    from generate.base import SamplerRNG, next_token
+    from lit_gpt import ops
+
+    sampling = temperature > 0.0
+    if sampling and top_k is None:
+        raise NotImplementedError("without top_k generate_speculative is greedy only: speculative sampling runs on "
+                                  f"the device top-k sampler (top_k 1..{ops.MAX_TOP_K})")
+    if sampling and not 1 <= top_k <= ops.MAX_TOP_K:
+        raise NotImplementedError(f"speculative sampling runs on the device top-k sampler: top_k must be in "
+                                  f"1..{ops.MAX_TOP_K}, got {top_k}")
     if not 1 <= speculate <= GPT.MAX_WINDOW - 1:
         raise ValueError(f"speculate must be in 1..{GPT.MAX_WINDOW - 1} (a verify window holds {GPT.MAX_WINDOW} rows)")
     T = prompt.size(0)
@@ -198,24 +244,31 @@ def generate_speculative(model: GPT, prompt: torch.Tensor, max_returned_tokens: 
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     c = model.config
-    from lit_gpt import ops
+    from generate.base import graph_sampling
     from lit_gpt.runtime import WindowDecodeGraph
 
     # everything the verify step refuses is refused here, before the prefill
     model._rows_check("speculative decoding")
+    if sampling and not graph_sampling(model, temperature, top_k):
+        raise NotImplementedError("speculative sampling runs on the device top-k sampler: bf16 logits of at most "
+                                  f"{ops.MAX_SAMPLE_VOCAB} entries (this model: {c.padded_vocab_size})")
     if not ops.decode_fusable(c.head_size, c.rope_n_elem) or c.n_head // c.n_query_groups not in (1, 2, 4, 8):
         raise NotImplementedError("speculative decoding needs the fused decode attention's geometry (head_size == "
                                   "rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group)")
     if hasattr(drafter, "check"):
         drafter.check(model)
     device = prompt.device
-    token = next_token(model, torch.arange(0, T, device=device), prompt.view(1, -1), temperature=0.0).clone()
+    rng = (rng or SamplerRNG(device)) if sampling else None
+    if hasattr(drafter, "set_sampling"):
+        drafter.set_sampling(temperature, top_k, rng.seed if sampling else 0)
+    kw = dict(temperature=temperature, top_k=top_k, rng=rng) if sampling else dict(temperature=0.0)
+    token = next_token(model, torch.arange(0, T, device=device), prompt.view(1, -1), **kw).clone()
     n_steps = max_returned_tokens - T - 1
     if n_steps <= 0:
         return torch.cat([prompt, token])
     tokens = prompt.tolist() + [int(token)]
     drafter.begin(prompt, tokens[-1])
-    ex = WindowDecodeGraph(model, token, T, use_graph=use_graph)
+    ex = WindowDecodeGraph(model, token, T, use_graph=use_graph, **(kw if sampling else {}))
     new = speculative_rounds(ex, drafter, tokens, n_steps, model.max_seq_length, speculate, eos_id, stats)
     return torch.cat([prompt, token, torch.tensor(new, dtype=prompt.dtype, device=device)])
 
@@ -226,14 +279,17 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
          quantize: Optional[str] = "int4-g128", precision: Optional[str] = None, synthetic: Optional[str] = None,
          prompt_len: int = 16, draft: Optional[str] = None, draft_checkpoint_dir: Optional[Path] = None,
          draft_synthetic: Optional[str] = None, draft_quantize: Optional[str] = "int4-g128",
-         speculate: int = DEFAULT_SPECULATE, temperature: float = 0.0, kv_cache: str = "bf16") -> None:
-    """``kv_cache`` is the TARGET's cache format (generate/base.py ``--kv_cache``); a draft model keeps bf16."""
+         speculate: int = DEFAULT_SPECULATE, temperature: float = 0.0, top_k: Optional[int] = None,
+         kv_cache: str = "bf16") -> None:
+    """``kv_cache`` is the TARGET's cache format (generate/base.py ``--kv_cache``); a draft model keeps bf16.
+    ``temperature`` > 0 needs ``top_k`` in 1..1024 and prints what generate/base.py prints at that setting."""
     from generate.base import build_model
+    from lit_gpt import ops
 
     if (precision or "bf16-true") != "bf16-true":
         raise NotImplementedError("speculative decoding runs 4-bit weights under bf16-true")
-    if temperature > 0.0:
-        raise NotImplementedError("generate/speculative.py is greedy only (temperature 0)")
+    if temperature > 0.0 and (top_k is None or not 1 <= top_k <= ops.MAX_TOP_K):
+        raise NotImplementedError("without --top_k in 1..1024 generate/speculative.py is greedy only (temperature 0)")
     kinds = [draft is not None, draft_checkpoint_dir is not None, draft_synthetic is not None]
     if sum(kinds) != 1:
         raise ValueError("choose one drafter: --draft ngram, --draft_checkpoint_dir DIR or --draft_synthetic NAME")
@@ -277,10 +333,11 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
     print(f"Time to load the model weights: {time.perf_counter() - t0:.02f} seconds.", file=sys.stderr)
     eos_id = tokenizer.eos_id if tokenizer is not None else None
     stats: Dict[str, int] = {}
+    torch.manual_seed(1234)  # as generate/base.py's main: the sampler's seed is drawn from torch's generator
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     y = generate_speculative(model, encoded, max_returned_tokens, drafter, speculate=speculate, eos_id=eos_id,
-                             stats=stats)
+                             stats=stats, temperature=temperature, top_k=top_k)
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
     print(tokenizer.decode(y) if tokenizer is not None else y.tolist())
@@ -294,15 +351,18 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
 
 
 def parse_args(argv=None) -> argparse.Namespace:
-    p = argparse.ArgumentParser(description="Greedy speculative decoding: the tokens of generate/base.py at "
-                                            "temperature 0, in fewer target-model passes.")
+    p = argparse.ArgumentParser(description="Speculative decoding: the tokens of generate/base.py at temperature 0, "
+                                            "or at --temperature T --top_k K with the same seed, in fewer "
+                                            "target-model passes.")
     p.add_argument("--prompt", default="What food do llamas eat?")
     p.add_argument("--max_new_tokens", type=int, default=50)
     p.add_argument("--checkpoint_dir", type=Path, default=Path("checkpoints/stabilityai/stablelm-base-alpha-3b"))
     p.add_argument("--quantize", default="int4-g128", help="the target's 4-bit format (the verify window streams "
                                                            "plain 4-bit Linears)")
     p.add_argument("--precision", default=None)
-    p.add_argument("--temperature", type=float, default=0.0, help="must stay 0: greedy only")
+    p.add_argument("--temperature", type=float, default=0.0,
+                   help="0: greedy; > 0 samples as generate/base.py does and needs --top_k")
+    p.add_argument("--top_k", type=int, default=None, help="with --temperature > 0: sample among the top_k (1..1024)")
     p.add_argument("--synthetic", default=None, help="random-init target of this registered config name")
     p.add_argument("--prompt_len", type=int, default=16)
     p.add_argument("--draft", default=None, choices=["ngram"], help="prompt-lookup drafting on the host")
@@ -318,8 +378,10 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error("choose one drafter: --draft ngram, --draft_checkpoint_dir DIR or --draft_synthetic NAME")
     if not 1 <= a.speculate <= GPT.MAX_WINDOW - 1:
         p.error(f"--speculate must be in 1..{GPT.MAX_WINDOW - 1}")
-    if a.temperature > 0.0:
-        p.error("--temperature must be 0: speculative decoding here is greedy only")
+    if a.top_k is not None and not 1 <= a.top_k <= 1024:
+        p.error("--top_k must be in 1..1024 (the device top-k sampler)")
+    if a.temperature > 0.0 and a.top_k is None:
+        p.error("--temperature > 0 needs --top_k in 1..1024: without it speculative decoding here is greedy only")
     return a
 
 
@@ -328,7 +390,8 @@ def _cli(argv=None) -> None:
     main(a.prompt, max_new_tokens=a.max_new_tokens, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize,
          precision=a.precision, synthetic=a.synthetic, prompt_len=a.prompt_len, draft=a.draft,
          draft_checkpoint_dir=a.draft_checkpoint_dir, draft_synthetic=a.draft_synthetic,
-         draft_quantize=a.draft_quantize, speculate=a.speculate, temperature=a.temperature, kv_cache=a.kv_cache)
+         draft_quantize=a.draft_quantize, speculate=a.speculate, temperature=a.temperature, top_k=a.top_k,
+         kv_cache=a.kv_cache)
 
 
 if __name__ == "__main__":

@@ -118,6 +118,7 @@ SIGNATURES = {
     "lga_f32_attention": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "lga_argmax_f32": [_P, _I, _P, _P, _P, _P],
     "lga_sample_topk": [_P, _I, _I, _F, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "lga_spec_accept_sample": [_P, _I, _I, _I, _F, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _P, _P],
     "lga_q4_gemv_allreduce": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(_P), _I, _I, _I, _P, _P, _P,
                               _P],
     "lga_q4_gemv_allreduce_tagged": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(_P), _I, _I, _I, _P, _P,
@@ -996,6 +997,61 @@ def sample_topk(logits, top_k, temperature, *, uniform=None, seed=0, counter=Non
         _opt(table, "table", torch.bfloat16), C, V, _opt(emb_out, "emb_out", torch.bfloat16),
         _opt(kept_out, "kept_out", torch.int32), _opt(probs_out, "probs_out", torch.bfloat16), _stream()))
     return idx
+
+
+_U64 = 2**64 - 1
+
+
+def sampler_uniform(seed: int, n: int) -> float:
+    """The uniform the device sampler uses for draw number ``n`` under ``seed`` (csrc/sample.hip draw_uniform), on
+    the host: ``((mix64(seed ^ n * 0xD1B54A32D192ED03) >> 41) + 0.5) * 2**-23`` in 64-bit wrap-around arithmetic,
+    mix64 the splitmix64 finaliser. 24 significant bits, so the value is exact in fp32 and lies in (0, 1)."""
+    x = ((int(seed) & _U64) ^ (((int(n) & _U64) * 0xD1B54A32D192ED03) & _U64))
+    x = (x + 0x9E3779B97F4A7C15) & _U64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _U64
+    x ^= x >> 31
+    return ((x >> 41) + 0.5) * 2.0**-23
+
+
+def spec_accept_sample(logits, window, top_k, temperature, *, uniform=None, seed=0, counter=None, out=None,
+                       token_inout=None, pos_inout=None, sampled=None):
+    """``spec_accept`` under top-k sampling (csrc/sample.hip lga_spec_accept_sample). logits (M, n) bf16, window (M,)
+    int32: t_r = the token ``sample_topk`` draws from logits[r] at ``top_k`` / ``temperature`` under ``uniform[r]``
+    (``uniform`` (M,) fp32 on the device), or otherwise under draw number ``counter + r`` of ``seed`` (``counter``
+    (1,) int64 on the device, the tokens sampled so far); a = the number of leading drafts with window[r + 1] == t_r.
+    Returns out (M + 1,) int32 = [a, t_0 .. t_a, -1 ...]; ``token_inout`` receives t_a, ``pos_inout`` advances by
+    a + 1 and so does ``counter``. The M rows are sampled by M concurrent workgroups, then one small launch accepts;
+    ``sampled`` (8,) int32 is the scratch between the two (allocated when omitted)."""
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= MAX_WINDOW_ROWS:
+        raise ValueError(f"spec_accept_sample: logits must be (M, n) with 1 <= M <= {MAX_WINDOW_ROWS}, "
+                         f"got {tuple(logits.shape)}")
+    M, n = logits.shape
+    if not 0 < n <= MAX_SAMPLE_VOCAB:
+        raise ValueError(f"spec_accept_sample: rows hold {n} logits, the sampler takes 1..{MAX_SAMPLE_VOCAB}")
+    if window.numel() != M:
+        raise ValueError(f"spec_accept_sample: window holds {window.numel()} tokens for {M} rows of logits")
+    if not 1 <= top_k <= MAX_TOP_K:
+        raise ValueError(f"spec_accept_sample: top_k must be in [1, {MAX_TOP_K}], got {top_k}")
+    if not temperature > 0.0:
+        raise ValueError("spec_accept_sample: temperature must be > 0 (0 is spec_accept)")
+    if uniform is None and counter is None:
+        raise ValueError("spec_accept_sample: needs uniforms or an RNG counter")
+    if uniform is not None and uniform.numel() != M:
+        raise ValueError(f"spec_accept_sample: {uniform.numel()} uniforms for {M} rows of logits")
+    lp = _dev(logits, "logits", torch.bfloat16)
+    res = out if out is not None else torch.empty(M + 1, dtype=torch.int32, device=logits.device)
+    if res.numel() < M + 1:
+        raise ValueError("spec_accept_sample: out needs M + 1 int32 values")
+    tmp = sampled if sampled is not None else torch.empty(MAX_WINDOW_ROWS, dtype=torch.int32, device=logits.device)
+    if tmp.numel() < M:
+        raise ValueError("spec_accept_sample: sampled needs one int32 per row")
+    _check(load_library().lga_spec_accept_sample(
+        lp, M, n, int(top_k), float(temperature), _opt(uniform, "uniform", torch.float32), int(seed) & _U64,
+        _opt(counter, "counter", torch.int64), _dev(window, "window", torch.int32), _dev(tmp, "sampled", torch.int32),
+        _dev(res, "out", torch.int32), _opt(token_inout, "token_inout", torch.int32),
+        _opt(pos_inout, "pos_inout", torch.int64), _stream()))
+    return res
 
 
 # ------------------------------------------------------------------------------------------------ scoring

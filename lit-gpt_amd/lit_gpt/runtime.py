@@ -120,22 +120,29 @@ class DecodeGraph:
 
 
 class WindowDecodeGraph:
-    """The verify step of greedy speculative decoding (generate/speculative.py) for one sequence: device-resident
+    """The verify step of speculative decoding (generate/speculative.py) for one sequence: device-resident
     ``window`` (MAX_WINDOW,) int32 — ``window[0]`` the last emitted token, ``window[1:M]`` the drafts — and ``pos``
     (1,), the position of ``window[0]``. A step over M = 1 + len(drafts) rows is embedding -> ``GPT.decode_window`` ->
     ``ops.spec_accept``, every launch on one stream: one unbranched HIP graph per M in use, captured lazily (the first
     step at an M runs eagerly and is then captured; the last windows of a run are shorter). ``spec_accept`` leaves
     the accepted count and the emitted tokens in ``out``, writes the last of them to ``window[0]`` and advances
     ``pos``, so the host reads ``out`` once per round and nothing per token. ``use_graph=False`` keeps every step
-    eager (tests A/B the two)."""
+    eager (tests A/B the two). ``temperature`` > 0 ends the step in ``ops.spec_accept_sample`` instead (``top_k``
+    1..1024, RNG state ``rng``: generate.base.SamplerRNG, whose counter is the number of tokens sampled so far): row r
+    is sampled with draw number counter + r and a draft is accepted iff it is that sample."""
 
-    def __init__(self, model, first_token, first_pos: int, *, use_graph: bool = True) -> None:
+    def __init__(self, model, first_token, first_pos: int, *, use_graph: bool = True, temperature: float = 0.0,
+                 top_k: Optional[int] = None, rng=None) -> None:
         wte = model.transformer.wte.weight
         dev = wte.device
         if not (wte.is_cuda and wte.dtype == torch.bfloat16 and wte.is_contiguous() and wte.shape[1] % 8 == 0):
             raise NotImplementedError("speculative decoding needs a contiguous bf16 embedding table on the GPU with "
                                       "n_embd % 8 == 0")
         model._rows_check("a speculative verify window")  # refuse before any launch
+        self.temperature, self.top_k, self.rng = float(temperature), top_k, rng
+        if self.temperature > 0.0 and (rng is None or top_k is None or not 1 <= top_k <= ops.MAX_TOP_K):
+            raise ValueError("WindowDecodeGraph: sampling needs top_k in [1, 1024] and an rng "
+                             "(generate.base.SamplerRNG)")
         self.model, self.use_graph = model, use_graph
         self.max_rows = model.MAX_WINDOW
         self.window = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)
@@ -143,13 +150,20 @@ class WindowDecodeGraph:
         self.pos = torch.tensor([first_pos], dtype=torch.int64, device=dev)
         self.out = torch.zeros(self.max_rows + 1, dtype=torch.int32, device=dev)
         self.x_emb = torch.empty(self.max_rows, wte.shape[1], dtype=torch.bfloat16, device=dev)
+        # the row samples, between spec_accept_sample's two launches
+        self.sampled = torch.zeros(self.max_rows, dtype=torch.int32, device=dev) if self.temperature > 0.0 else None
         self.graphs = {}
 
     def _step_body(self, M: int) -> None:
         model, w = self.model, self.window[:M]
         x = ops.embedding(w, model.transformer.wte.weight, out=self.x_emb[:M])
         logits = model.decode_window(w, self.pos, embedded=x)
-        ops.spec_accept(logits, w, out=self.out[:M + 1], token_inout=self.window[:1], pos_inout=self.pos)
+        if self.temperature > 0.0:
+            ops.spec_accept_sample(logits, w, self.top_k, self.temperature, seed=self.rng.seed,
+                                   counter=self.rng.counter, out=self.out[:M + 1], token_inout=self.window[:1],
+                                   pos_inout=self.pos, sampled=self.sampled)
+        else:
+            ops.spec_accept(logits, w, out=self.out[:M + 1], token_inout=self.window[:1], pos_inout=self.pos)
 
     def step(self, drafts=()):
         """Verify ``drafts`` (a sequence of ints, or an int32 device tensor; at most MAX_WINDOW - 1 of them) after the

@@ -6,12 +6,23 @@ usage: python tools/spec_decode.py kernels [--out profiles/spec_kernels.json]
            run), Llama-2-7B geometry (32 heads, 32 groups) and one GQA geometry (32 heads, 8 groups) at p = 2048 in a
            2304-row cache. One graph of 32 "layers" over distinct caches, median of 7 replays.
            (b) the whole verify step (embedding -> decode_window -> spec_accept, one graph) of synthetic Llama-2-7B
-           int4-g128 at M = 1..8 against the one-row greedy step (DecodeGraph), p = 2048, median of 7 replays.
+           int4-g128 at M = 1..8 against the one-row greedy step (DecodeGraph), p = 2048, median of 7 replays; and
+           the same verify step under top-k sampling (spec_accept_sample in spec_accept's place) against the one-row
+           sampled step.
+           (s) us per call of lga_spec_accept_sample (the window sampler + the accept launch) at M = 1, 2, 4, 8
+           (n = 32000, top_k = 200, temperature 0.8) against M back-to-back lga_sample_topk launches. One graph of
+           32 calls over distinct logits, median of 7 replays.
        python tools/spec_decode.py e2e [--out profiles/spec_e2e.json] [--prompt_len 2048] [--steps 255]
+                                       [--temperature 0.8 --top_k 200]
            (c) synthetic Llama-2-7B int4-g128, greedy, decode tokens/s (prefill timed apart) of generate and of
            generate_speculative at gamma = 1, 3, 7 with a scripted drafter forced to 0 %, ~50 % and 100 % acceptance
            (it knows generate's output), and the 100 % rows again with a 4-layer synthetic draft model's drafting
            time included. Random synthetic weights give no meaningful acceptance rate of their own: none is quoted.
+           With --temperature T --top_k K: the same under sampling (generate and generate_speculative with one
+           sampler seed), and in place of the 4-layer rows an nf4 twin of the target (same float weights) as
+           ModelDrafter, coupled (drafts sampled with the target's uniforms) and uncoupled (greedy drafts), with the
+           acceptance each reaches. That acceptance is a property of the synthetic weights (near-flat top-k
+           distributions), not of trained checkpoints.
 """
 import argparse
 import json
@@ -99,13 +110,45 @@ def attention(result, p=2048, max_seq=2304):
         torch.cuda.empty_cache()
 
 
-def _model(prompt_len, steps, **over):
+def _model(prompt_len, steps, quantize="int4-g128", **over):
     from generate.base import build_model
     from lit_gpt import Config
 
     cfg = Config.from_name("Llama-2-7b-hf", **over)
-    return build_model(cfg, quantize="int4-g128", device=torch.device("cuda"), max_seq_length=prompt_len + steps + 1,
+    return build_model(cfg, quantize=quantize, device=torch.device("cuda"), max_seq_length=prompt_len + steps + 1,
                        seed=4321 if over else 1234)
+
+
+def sampler(result, n=32000, top_k=200, temperature=0.8, calls=32):
+    dev = torch.device("cuda")
+    logits = [(torch.randn(8, n, device=dev) * 3.0).bfloat16() for _ in range(calls)]
+    window = torch.zeros(8, dtype=torch.int32, device=dev)
+    out = torch.zeros(9, dtype=torch.int32, device=dev)
+    sampled = torch.zeros(8, dtype=torch.int32, device=dev)
+    idx = torch.zeros(8, dtype=torch.int64, device=dev)
+    counter = torch.zeros(1, dtype=torch.int64, device=dev)
+    row = {"n": n, "top_k": top_k, "temperature": temperature}
+
+    def one_row(M):
+        def run():
+            for lg in logits:
+                for r in range(M):
+                    ops.sample_topk(lg[r], top_k, temperature, seed=1234, counter=counter, out_idx=idx[r:r + 1])
+        return run
+
+    def entry(M):
+        def run():
+            for lg in logits:
+                ops.spec_accept_sample(lg[:M], window[:M], top_k, temperature, seed=1234, counter=counter,
+                                       out=out[:M + 1], sampled=sampled)
+        return run
+
+    for M in (1, 2, 4, 8):
+        row[f"window_{M}_us"] = _median_us(entry(M), calls)  # (both launches of the entry)
+        row[f"one_row_x{M}_us"] = _median_us(one_row(M), calls)
+        row[f"ok_{M}"] = bool(M == 1 or row[f"window_{M}_us"] < row[f"one_row_x{M}_us"])
+    result["sampler"] = row
+    print("sampler", json.dumps(row), flush=True)
 
 
 def _prompt(model, prompt_len):
@@ -113,7 +156,8 @@ def _prompt(model, prompt_len):
     return torch.randint(0, model.config.vocab_size, (prompt_len,), generator=g, dtype=torch.int32).to("cuda")
 
 
-def step(result, prompt_len=2048):
+def step(result, prompt_len=2048, top_k=200, temperature=0.8):
+    from generate.base import SamplerRNG
     from lit_gpt.runtime import DecodeGraph, WindowDecodeGraph
 
     model = _model(prompt_len, 64)
@@ -130,23 +174,46 @@ def step(result, prompt_len=2048):
             ex.pos.fill_(prompt_len)
             row[f"window_step_{M}_us"] = _replay_us(ex.graphs[M])
             row[f"ratio_{M}"] = row[f"window_step_{M}_us"] / row["one_row_step_us"]
+        # the same under top-k sampling: the one-row sampled step, and the window step ending in spec_accept_sample
+        sdg = DecodeGraph(model, first, prompt_len, temperature=temperature, top_k=top_k,
+                          rng=SamplerRNG(first.device, seed=1234))
+        row["one_row_sampled_step_us"] = _replay_us(sdg.graph)
+        sex = WindowDecodeGraph(model, first, prompt_len, temperature=temperature, top_k=top_k,
+                                rng=SamplerRNG(first.device, seed=1234))
+        for M in range(1, model.MAX_WINDOW + 1):
+            sex.pos.fill_(prompt_len)
+            sex.step([1] * (M - 1))
+            sex.pos.fill_(prompt_len)
+            row[f"window_sampled_step_{M}_us"] = _replay_us(sex.graphs[M])
+            row[f"sampled_minus_greedy_{M}_us"] = row[f"window_sampled_step_{M}_us"] - row[f"window_step_{M}_us"]
     result["step"] = row
     print("step", json.dumps(row), flush=True)
 
 
-def kernels(out, skip_step):
+def kernels(out, skip_step, skip_attention=False):
     result = {"what": "us, median of 7 graph replays; attention: per launch over 32 distinct caches, one_row_xM = M "
-                      "back-to-back one-row launches on one cache; step: synthetic Llama-2-7B int4-g128 at p = 2048",
+                      "back-to-back one-row launches on one cache; sampler: per lga_spec_accept_sample call over 32 "
+                      "distinct logits, one_row_xM = M back-to-back lga_sample_topk launches; step: synthetic "
+                      "Llama-2-7B int4-g128 at p = 2048",
               "library": os.environ.get("LGA_LIB", "default build"), "attention": {}}
-    attention(result)
+    if not skip_attention:
+        attention(result)
+    sampler(result)
     if not skip_step:
         step(result)
     _write(out, result)
 
 
-def e2e(out, prompt_len, steps):
-    from generate.base import generate
+def e2e(out, prompt_len, steps, temperature=0.0, top_k=None):
+    from generate.base import SamplerRNG, generate
     from generate.speculative import ModelDrafter, ScriptedDrafter, generate_speculative
+
+    sampling = temperature > 0.0
+
+    def kw():  # greedy, or sampling with one seed (a fresh counter per run)
+        if not sampling:
+            return dict(temperature=0.0)
+        return dict(temperature=temperature, top_k=top_k, rng=SamplerRNG(torch.device("cuda"), seed=1234))
 
     model = _model(prompt_len, steps)
     prompt = _prompt(model, prompt_len)
@@ -167,12 +234,15 @@ def e2e(out, prompt_len, steps):
         dec = statistics.median(full) - pre
         return {"prefill_s": pre, "decode_s": dec, "tokens_per_s": steps / dec}
 
-    ref = generate(model, prompt, prompt_len + new, temperature=0.0).tolist()
-    result = {"what": "synthetic Llama-2-7B int4-g128, greedy; decode time = run(steps + 1 tokens) - run(1 token), "
-                      "median of 3 after a warm-up; acceptance forced by a scripted drafter",
+    ref = generate(model, prompt, prompt_len + new, **kw()).tolist()
+    mode = f"top-k sampling (temperature {temperature}, top_k {top_k}, one seed)" if sampling else "greedy"
+    result = {"what": f"synthetic Llama-2-7B int4-g128, {mode}; decode time = run(steps + 1 tokens) - run(1 token), "
+                      "median of 3 after a warm-up; acceptance forced by a scripted drafter"
+                      + (", or reached by an nf4 twin of the target as ModelDrafter (synthetic weights: says nothing "
+                         "about trained checkpoints)" if sampling else ""),
               "prompt_len": prompt_len, "steps": steps, "rows": []}
-    base = measure(lambda: generate(model, prompt, prompt_len + new, temperature=0.0),
-                   lambda: generate(model, prompt, prompt_len + 1, temperature=0.0))
+    base = measure(lambda: generate(model, prompt, prompt_len + new, **kw()),
+                   lambda: generate(model, prompt, prompt_len + 1, **kw()))
     result["generate"] = base
     print("generate", json.dumps(base), flush=True)
 
@@ -188,21 +258,28 @@ def e2e(out, prompt_len, steps):
             self.md.propose(tokens, k)
             return self.scripted.propose(tokens, k)
 
-    draft_model = _model(prompt_len, steps, n_layer=4)
+    # greedy: a 4-layer draft model's drafting time; sampling: the target's nf4 twin as the drafter itself
+    draft_model = _model(prompt_len, steps, quantize="nf4") if sampling else _model(prompt_len, steps, n_layer=4)
     for gamma in (1, 3, 7):
         half = gamma // 2
         patterns = {"0%": lambda rnd, i: True, "50%": lambda rnd, i: i == half + (rnd % 2) * (gamma % 2),
                     "100%": lambda rnd, i: False}
-        for label, wrong in list(patterns.items()) + [("100% + 4-layer draft model", patterns["100%"])]:
+        extra = ([("nf4 twin, coupled", None), ("nf4 twin, uncoupled", None)] if sampling
+                 else [("100% + 4-layer draft model", patterns["100%"])])
+        for label, wrong in list(patterns.items()) + extra:
             def drafter():
+                if wrong is None:
+                    return ModelDrafter(draft_model, coupled="uncoupled" not in label)
                 d = ScriptedDrafter(ref, wrong, V)
                 return Timed(d, ModelDrafter(draft_model)) if "draft model" in label else d
 
             stats = {}
-            y = generate_speculative(model, prompt, prompt_len + new, drafter(), speculate=gamma, stats=stats)
+            y = generate_speculative(model, prompt, prompt_len + new, drafter(), speculate=gamma, stats=stats, **kw())
             assert y.tolist() == ref, (gamma, label)
-            row = measure(lambda: generate_speculative(model, prompt, prompt_len + new, drafter(), speculate=gamma),
-                          lambda: generate_speculative(model, prompt, prompt_len + 1, drafter(), speculate=gamma))
+            row = measure(lambda: generate_speculative(model, prompt, prompt_len + new, drafter(), speculate=gamma,
+                                                       **kw()),
+                          lambda: generate_speculative(model, prompt, prompt_len + 1, drafter(), speculate=gamma,
+                                                       **kw()))
             row.update(gamma=gamma, forced=label, rounds=stats["rounds"], proposed=stats["proposed"],
                        accepted=stats["accepted"], tokens_per_pass=stats["tokens"] / stats["rounds"],
                        speedup=row["tokens_per_s"] / base["tokens_per_s"])
@@ -226,10 +303,15 @@ if __name__ == "__main__":
     p.add_argument("--steps", type=int, default=255)
     p.add_argument("--skip_step", action="store_true", help="kernels: the attention launches only (with LGA_LIB set "
                                                             "to a lab build, e.g. -DLGA_ATTN_WIN_NT=1: the load-hint A/B)")
+    p.add_argument("--skip_attention", action="store_true", help="kernels: leave the attention table out")
+    p.add_argument("--temperature", type=float, default=0.0, help="e2e: > 0 measures under top-k sampling")
+    p.add_argument("--top_k", type=int, default=None, help="e2e: with --temperature, 1..1024")
     a = p.parse_args()
+    if a.temperature > 0.0 and (a.top_k is None or not 1 <= a.top_k <= 1024):
+        p.error("--temperature > 0 needs --top_k in 1..1024")
     if not torch.cuda.is_available():
         sys.exit("spec_decode.py measures on the GPU; there is none here")
     if a.mode == "kernels":
-        kernels(a.out, a.skip_step)
+        kernels(a.out, a.skip_step, a.skip_attention)
     else:
-        e2e(a.out, a.prompt_len, a.steps)
+        e2e(a.out, a.prompt_len, a.steps, a.temperature, a.top_k)
