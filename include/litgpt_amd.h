@@ -248,6 +248,26 @@ int lga_attention_decode_window_kv8(const void* qkv, void* k_codes, void* v_code
                                     float* workspace, unsigned* counters, int M, int n_head, int n_query_groups,
                                     int head_size, int rope_n_elem, int max_seq, int n_splits, float scale,
                                     lga_stream_t stream);
+/* -- batched decode attention -------------------------------------------------------------------------------------
+ * B (1..8) independent sequences in ONE launch. Row b reads row b of the (B, (H + 2G) hs) qkv, sits at cache_pos[b]
+ * / rope_pos[b] and owns cache slot b: k_cache + b * slot_stride, v_cache + b * slot_stride (and for the fp8 cache
+ * k_scale / v_scale + b * scale_slot_stride); strides in elements, the (B, G, max_seq, hs) tensor's stride(0), at
+ * least G * max_seq * hs (G * max_seq for the scales). Row b's y (B, H*hs), cache rows and scale rows have the bits of
+ * lga_attention_decode_fused(_kv8) on that row and slot with the same n_splits; no other slot is read or written. A
+ * row at or past max_seq stores nothing and attends keys 0..max_seq-1. active (B) int32 may be null (every row
+ * active); a row with active[b] == 0 is idle: y[b] = 0 and its slot stays bit-unchanged. workspace: lga_attention_
+ * workspace_bytes(B, ...); counters B * n_head * 64 uint32, zeroed once. Same geometry limits as the fused forms. */
+int lga_attention_decode_batch(const void* qkv, void* k_cache, void* v_cache, const int64_t* cache_pos,
+                               const int64_t* rope_pos, const float* cos, const float* sin, int rope_rows, void* y,
+                               float* workspace, unsigned* counters, int B, long long slot_stride,
+                               const int32_t* active, int n_head, int n_query_groups, int head_size, int rope_n_elem,
+                               int max_seq, int n_splits, float scale, lga_stream_t stream);
+int lga_attention_decode_batch_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                                   const int64_t* cache_pos, const int64_t* rope_pos, const float* cos,
+                                   const float* sin, int rope_rows, void* y, float* workspace, unsigned* counters,
+                                   int B, long long slot_stride, long long scale_slot_stride, const int32_t* active,
+                                   int n_head, int n_query_groups, int head_size, int rope_n_elem, int max_seq,
+                                   int n_splits, float scale, lga_stream_t stream);
 /* lga_rope_kv_append for fp8 caches (T rows): roped q to q_out (T, H, hs); k (roped) and v quantized into the codes
  * and scales at row cache_pos[t] — the bits the decode forms store for the same qkv row. */
 int lga_kv8_rope_append(const void* qkv, void* q_out, void* k_codes, void* v_codes, float* k_scale, float* v_scale,

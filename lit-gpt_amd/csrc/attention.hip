@@ -93,15 +93,27 @@ struct kv_regs<true> {
 #define LGA_ATTN_WIN_NT 0  // lab A/B: 1 = the one-row kernel's nt loads in the window kernel too
 #endif
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE, bool WINDOW = false, bool KV8 = false>
+// BATCH (batched decode, lga_attention_decode_batch): B independent T = 1 FUSED workgroup sets in one launch; grid.z =
+// sequence b, with its own qkv row, its own position (input_pos[b], rope_pos[b]), its own cache slot (k / v + b *
+// slot_stride elements, the fp8 scale rows + b * scale_slot_stride) and its own append, exactly the one-row form's:
+// no row reads what another row writes, so unlike WINDOW there is no separate append launch. Workspace and counters
+// are indexed by t = b as for any multi-row launch. A row with active[b] == 0 is idle: every one of its workgroups
+// returns before any K/V load, store, workspace write or counter add (the test is uniform per workgroup and sits ahead
+// of every barrier, so the counter protocol of the other rows is untouched), the split-0 workgroups having zeroed
+// their heads of y[b].
+template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE, bool WINDOW = false, bool KV8 = false,
+          bool BATCH = false>
 __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc,
                                           uint16_t* __restrict__ vc, const int64_t* __restrict__ input_pos,
                                           uint16_t* __restrict__ y, float* __restrict__ ws,
                                           unsigned* __restrict__ cnt, int n_head, int max_seq, float scale,
                                           const int64_t* __restrict__ rope_pos, const float* __restrict__ cos,
                                           const float* __restrict__ sin, int rope_rows, int hsplit,
-                                          float* __restrict__ ksc = nullptr, float* __restrict__ vsc = nullptr) {
+                                          float* __restrict__ ksc = nullptr, float* __restrict__ vsc = nullptr,
+                                          long slot_stride = 0, long scale_slot_stride = 0,
+                                          const int* __restrict__ active = nullptr) {
   static_assert(!KV8 || (FUSED && HS == 128), "the fp8 cache serves the fused decode forms");
+  static_assert(!BATCH || (FUSED && !WINDOW), "the batch form is the fused one-row form per sequence");
   constexpr int LPR = HS / 8;    // lanes per key row
   constexpr int RGW = 64 / LPR;  // row groups per wave
   constexpr int RG = NW * RGW;   // row groups per workgroup
@@ -119,7 +131,22 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   static_assert(!WINDOW || FUSED, "the window form is the fused form per row");
   const long p = WINDOW ? input_pos[0] + t : input_pos[t];
   const long rp_raw = WINDOW ? p : (FUSED ? rope_pos[t] : 0);
-  if (WINDOW) q += (size_t)t * (n_head + 2 * (gridDim.y / hsplit)) * HS;  // row t of the (M, (H + 2G) hs) qkv
+  if (WINDOW || BATCH) q += (size_t)t * (n_head + 2 * (gridDim.y / hsplit)) * HS;  // row t of the (M, (H + 2G) hs) qkv
+  if constexpr (BATCH) {
+    if (active != nullptr && active[t] == 0) {  // idle row: zero y[t] (split 0), touch nothing else
+      constexpr int NQ0 = QPK * HS / 4;
+      if (split == 0 && threadIdx.x < NQ0)
+        *(uint2*)(y + ((size_t)t * n_head + (size_t)g * QPKT + hsi * QPK) * HS + threadIdx.x * 4) = make_uint2(0u, 0u);
+      return;
+    }
+    // sequence t's slot: KV8 codes are bytes behind the uint16_t pointers, bf16 rows are elements
+    kc = KV8 ? (uint16_t*)((uint8_t*)kc + (size_t)t * slot_stride) : kc + (size_t)t * slot_stride;
+    vc = KV8 ? (uint16_t*)((uint8_t*)vc + (size_t)t * slot_stride) : vc + (size_t)t * slot_stride;
+    if constexpr (KV8) {
+      ksc += (size_t)t * scale_slot_stride;
+      vsc += (size_t)t * scale_slot_stride;
+    }
+  }
   const int L = (int)min(p + 1, (long)max_seq);  // keys 0..p (never past the cache)
   const int chunk = (L + n_splits - 1) / n_splits;
   const int k_lo = split * chunk;
@@ -447,19 +474,22 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   LGA_TRACE(6);
 }
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool PIPE, bool WINDOW = false>
+// (BATCH sits ahead of FUSED: the mangled names of the other forms keep their <.., FUSED, PIPE, WINDOW> tail)
+template <int HS, int QPK, int UNR, int NW, bool BATCH, bool FUSED, bool PIPE, bool WINDOW = false>
 __global__ void __launch_bounds__(NW * 64) attn_kernel(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc,
                                                    uint16_t* __restrict__ vc, const int64_t* __restrict__ input_pos,
                                                    uint16_t* __restrict__ y, float* __restrict__ ws,
                                                    unsigned* __restrict__ cnt, int n_head, int max_seq, float scale,
                                                    const int64_t* __restrict__ rope_pos, const float* __restrict__ cos,
-                                                   const float* __restrict__ sin, int rope_rows, int hsplit) {
-  attn_body<HS, QPK, UNR, NW, FUSED, PIPE, WINDOW>(q, kc, vc, input_pos, y, ws, cnt, n_head, max_seq, scale, rope_pos,
-                                                   cos, sin, rope_rows, hsplit);
+                                                   const float* __restrict__ sin, int rope_rows, int hsplit,
+                                                   long slot_stride, const int* __restrict__ active) {
+  attn_body<HS, QPK, UNR, NW, FUSED, PIPE, WINDOW, false, BATCH>(q, kc, vc, input_pos, y, ws, cnt, n_head, max_seq,
+                                                                 scale, rope_pos, cos, sin, rope_rows, hsplit, nullptr,
+                                                                 nullptr, slot_stride, 0, active);
 }
 
-// the fp8-cache instantiations (FUSED one-row and WINDOW): attn_kernel plus the two scale arrays
-template <int HS, int QPK, int UNR, int NW, bool PIPE, bool WINDOW>
+// the fp8-cache instantiations (FUSED one-row, WINDOW and BATCH): attn_kernel plus the two scale arrays
+template <int HS, int QPK, int UNR, int NW, bool BATCH, bool PIPE, bool WINDOW>
 __global__ void __launch_bounds__(NW * 64) attn_kernel_kv8(const uint16_t* __restrict__ q, uint8_t* __restrict__ kc,
                                                        uint8_t* __restrict__ vc, float* __restrict__ ksc,
                                                        float* __restrict__ vsc, const int64_t* __restrict__ input_pos,
@@ -467,10 +497,12 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel_kv8(const uint16_t* __res
                                                        unsigned* __restrict__ cnt, int n_head, int max_seq, float scale,
                                                        const int64_t* __restrict__ rope_pos,
                                                        const float* __restrict__ cos, const float* __restrict__ sin,
-                                                       int rope_rows, int hsplit) {
-  attn_body<HS, QPK, UNR, NW, true, PIPE, WINDOW, true>(q, (uint16_t*)kc, (uint16_t*)vc, input_pos, y, ws, cnt, n_head,
-                                                        max_seq, scale, rope_pos, cos, sin, rope_rows, hsplit, ksc,
-                                                        vsc);
+                                                       int rope_rows, int hsplit, long slot_stride,
+                                                       long scale_slot_stride, const int* __restrict__ active) {
+  attn_body<HS, QPK, UNR, NW, true, PIPE, WINDOW, true, BATCH>(q, (uint16_t*)kc, (uint16_t*)vc, input_pos, y, ws, cnt,
+                                                               n_head, max_seq, scale, rope_pos, cos, sin, rope_rows,
+                                                               hsplit, ksc, vsc, slot_stride, scale_slot_stride,
+                                                               active);
 }
 
 // The window's KV-append: roped k and v of row r into cache row pos0[0] + r of every group, with the fused kernel's
@@ -1089,18 +1121,25 @@ __global__ void __launch_bounds__(512, 1) attn_prefill_pair_kernel(const uint16_
 #define LGA_ATTN_Q8 2, 4
 #endif
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool WINDOW = false, bool KV8 = false>
+// the slot strides and the idle flags of a BATCH launch (zeros / null for every other form)
+struct BatchArgs {
+  long slot_stride = 0, scale_slot_stride = 0;
+  const int* active = nullptr;
+};
+
+template <int HS, int QPK, int UNR, int NW, bool FUSED, bool WINDOW = false, bool KV8 = false, bool BATCH = false>
 static void launch_one(dim3 grid, hipStream_t stream, const void* q, void* kc, void* vc, const int64_t* pos, void* y,
                        float* ws, unsigned* cnt, int H, int max_seq, float scale, const int64_t* rope_pos,
-                       const float* cos, const float* sin, int rope_rows, int hsplit, float* ksc, float* vsc) {
+                       const float* cos, const float* sin, int rope_rows, int hsplit, float* ksc, float* vsc,
+                       const BatchArgs& ba) {
   if constexpr (KV8) {
-    attn_kernel_kv8<HS, QPK, UNR, NW, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
+    attn_kernel_kv8<HS, QPK, UNR, NW, BATCH, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
         (const uint16_t*)q, (uint8_t*)kc, (uint8_t*)vc, ksc, vsc, pos, (uint16_t*)y, ws, cnt, H, max_seq, scale,
-        rope_pos, cos, sin, rope_rows, hsplit);
+        rope_pos, cos, sin, rope_rows, hsplit, ba.slot_stride, ba.scale_slot_stride, ba.active);
   } else {
-    attn_kernel<HS, QPK, UNR, NW, FUSED, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
+    attn_kernel<HS, QPK, UNR, NW, BATCH, FUSED, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
         (const uint16_t*)q, (uint16_t*)kc, (uint16_t*)vc, pos, (uint16_t*)y, ws, cnt, H, max_seq, scale, rope_pos, cos,
-        sin, rope_rows, hsplit);
+        sin, rope_rows, hsplit, ba.slot_stride, ba.active);
   }
 }
 
@@ -1119,15 +1158,17 @@ static int attn_hsplit(int T, int G, int qpk, int n_splits) {
   return h;
 }
 
-template <int HS, bool FUSED, bool WINDOW = false, bool KV8 = false>
+template <int HS, bool FUSED, bool WINDOW = false, bool KV8 = false, bool BATCH = false>
 static int launch_hs(const void* q, void* kc, void* vc, const int64_t* pos, void* y, float* ws, unsigned* cnt, int T,
                      int H, int G, int max_seq, int n_splits, float scale, const int64_t* rope_pos, const float* cos,
-                     const float* sin, int rope_rows, hipStream_t stream, float* ksc = nullptr, float* vsc = nullptr) {
-  const int hsplit = attn_hsplit(WINDOW ? 1 : T, G, H / G, n_splits);  // a window row: the slices of its T = 1 launch
+                     const float* sin, int rope_rows, hipStream_t stream, float* ksc = nullptr, float* vsc = nullptr,
+                     const BatchArgs& ba = BatchArgs()) {
+  // a window row, a batch row: the slices of its T = 1 launch
+  const int hsplit = attn_hsplit(WINDOW || BATCH ? 1 : T, G, H / G, n_splits);
   const dim3 grid(n_splits, G * hsplit, T);
 #define LGA_ATTN(QPK, CFG)                                                                                        \
-  launch_one<HS, QPK, CFG, FUSED, WINDOW, KV8>(grid, stream, q, kc, vc, pos, y, ws, cnt, H, max_seq, scale, rope_pos, cos, \
-                                       sin, rope_rows, hsplit, ksc, vsc)
+  launch_one<HS, QPK, CFG, FUSED, WINDOW, KV8, BATCH>(grid, stream, q, kc, vc, pos, y, ws, cnt, H, max_seq, scale,     \
+                                                      rope_pos, cos, sin, rope_rows, hsplit, ksc, vsc, ba)
   switch (H / G / hsplit) {
     case 1:  // one head per group: 8 waves x 2 keys in flight when the groups are few (TP ranks: G = 4 7.9 vs 8.2 us,
              // G = 8 8.0 vs 8.7 at 16 splits; profiles/r04u_attn_head_slices.txt), else 4 x 4 (Llama-2-7B, G = 32)
@@ -1301,6 +1342,62 @@ extern "C" int lga_attention_decode_window_kv8(const void* qkv, void* k_codes, v
   const int rc = lga::launch_hs<128, true, true, true>(qkv, k_codes, v_codes, pos0, y, workspace, counters, M, n_head,
                                                        n_query_groups, max_seq, n_splits, scale, pos0, cos, sin,
                                                        rope_rows, stream, k_scale, v_scale);
+  if (rc) return rc;
+  LGA_LAUNCH_RETURN();
+}
+
+// Batched decode step: B independent sequences in ONE launch, grid (n_splits, G * hsplit, B). Row b reads row b of
+// the (B, (H + 2G) hs) qkv, sits at cache_pos[b] / rope_pos[b] and owns the cache slot k_cache + b * slot_stride,
+// v_cache + b * slot_stride (strides in elements: the (B, G, max_seq, hs) cache tensor's stride(0)). Row b's y, cache
+// rows (and scale rows) have the bits of lga_attention_decode_fused(_kv8) on that row and slot with the same
+// n_splits; no other slot is read or written. active (B) int32 may be null (all rows active); a row with active[b]
+// == 0 is idle: y[b] = 0, its slot bit-unchanged. workspace / counters as for a T = B launch.
+extern "C" int lga_attention_decode_batch(const void* qkv, void* k_cache, void* v_cache, const int64_t* cache_pos,
+                                          const int64_t* rope_pos, const float* cos, const float* sin, int rope_rows,
+                                          void* y, float* workspace, unsigned* counters, int B, long long slot_stride,
+                                          const int32_t* active, int n_head, int n_query_groups, int head_size,
+                                          int rope_n_elem, int max_seq, int n_splits, float scale,
+                                          hipStream_t stream) {
+  LGA_CHECK_ARG(qkv && k_cache && v_cache && cache_pos && rope_pos && cos && sin && y,
+                "lga_attention_decode_batch: null pointer");
+  LGA_CHECK_ARG(B >= 1 && B <= 8, "lga_attention_decode_batch: B must be in [1, 8]");
+  LGA_KV8_COMMON("lga_attention_decode_batch");
+  LGA_CHECK_ARG(slot_stride >= (long long)n_query_groups * max_seq * head_size,
+                "lga_attention_decode_batch: slot_stride below one sequence's G * max_seq * head_size elements");
+  lga::BatchArgs ba;
+  ba.slot_stride = (long)slot_stride;
+  ba.active = active;
+  const int rc = lga::launch_hs<128, true, false, false, true>(qkv, k_cache, v_cache, cache_pos, y, workspace,
+                                                               counters, B, n_head, n_query_groups, max_seq, n_splits,
+                                                               scale, rope_pos, cos, sin, rope_rows, stream, nullptr,
+                                                               nullptr, ba);
+  if (rc) return rc;
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_attention_decode_batch_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale,
+                                              float* v_scale, const int64_t* cache_pos, const int64_t* rope_pos,
+                                              const float* cos, const float* sin, int rope_rows, void* y,
+                                              float* workspace, unsigned* counters, int B, long long slot_stride,
+                                              long long scale_slot_stride, const int32_t* active, int n_head,
+                                              int n_query_groups, int head_size, int rope_n_elem, int max_seq,
+                                              int n_splits, float scale, hipStream_t stream) {
+  LGA_CHECK_ARG(qkv && k_codes && v_codes && k_scale && v_scale && cache_pos && rope_pos && cos && sin && y,
+                "lga_attention_decode_batch_kv8: null pointer");
+  LGA_CHECK_ARG(B >= 1 && B <= 8, "lga_attention_decode_batch_kv8: B must be in [1, 8]");
+  LGA_KV8_COMMON("lga_attention_decode_batch_kv8");
+  LGA_CHECK_ARG(slot_stride >= (long long)n_query_groups * max_seq * head_size,
+                "lga_attention_decode_batch_kv8: slot_stride below one sequence's G * max_seq * head_size codes");
+  LGA_CHECK_ARG(scale_slot_stride >= (long long)n_query_groups * max_seq,
+                "lga_attention_decode_batch_kv8: scale_slot_stride below one sequence's G * max_seq scales");
+  lga::BatchArgs ba;
+  ba.slot_stride = (long)slot_stride;
+  ba.scale_slot_stride = (long)scale_slot_stride;
+  ba.active = active;
+  const int rc = lga::launch_hs<128, true, false, true, true>(qkv, k_codes, v_codes, cache_pos, y, workspace, counters,
+                                                              B, n_head, n_query_groups, max_seq, n_splits, scale,
+                                                              rope_pos, cos, sin, rope_rows, stream, k_scale, v_scale,
+                                                              ba);
   if (rc) return rc;
   LGA_LAUNCH_RETURN();
 }

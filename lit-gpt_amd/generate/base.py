@@ -244,6 +244,72 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
     return [torch.cat([p, f, out[:n_b, b].to(p.dtype)]) for b, (p, f, n_b) in enumerate(zip(prompts, firsts, lengths))]
 
 
+@torch.inference_mode()
+def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens, *, batch_size: int = MAX_BATCH,
+                        temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None,
+                        seeds: Optional[List[int]] = None, use_graph: bool = True,
+                        chunk: int = DECODE_CHUNK) -> List[torch.Tensor]:
+    """Continuous batching: any number of prompts (each (T_i,)) through ``min(batch_size, len(prompts))`` slots of the
+    batched decode step. ``max_new_tokens``: an int, or one per prompt. A prompt enters a free slot through the single
+    path's prefill; a sequence that met ``eos_id`` or its budget leaves its slot to the next prompt of the queue while
+    the other slots keep decoding, their state on the device (lit_gpt.runtime.SlotDecodeGraph; the bookkeeping is
+    lit_gpt.scheduler.SlotScheduler). Returns the (T_i + new_i,) ids in prompt order; ``result[i]`` is exactly what
+    ``generate(model, prompts[i], T_i + max_new_i, ..., rng=SamplerRNG(device, seeds[i]))`` returns on a cache of the
+    same ``max_seq_length``. Refuses what ``generate_batch`` refuses."""
+    from lit_gpt.scheduler import SlotScheduler
+
+    n = len(prompts)
+    if n == 0:
+        raise ValueError("generate_continuous: no prompts")
+    if batch_size < 1:
+        raise ValueError("generate_continuous: batch_size must be at least 1")
+    if batch_size > MAX_BATCH:
+        raise NotImplementedError(f"generate_continuous: batch_size {batch_size}; the MI355X batched decode runs at "
+                                  f"most {MAX_BATCH} sequences per step")
+    B = min(batch_size, n)
+    device = prompts[0].device
+    sampling = temperature > 0.0
+    if sampling and seeds is None:
+        seeds = [int(torch.randint(0, 2**62, (1,))) for _ in range(n)]  # as SamplerRNG draws its own
+    sched = SlotScheduler([p.size(0) for p in prompts], max_new_tokens, B, chunk=chunk, eos_id=eos_id, seeds=seeds if sampling else None, max_seq_length=model.max_seq_length)
+    budgets = [s + 1 for s in sched.steps_budget]
+    if B == 1:  # one slot: the single path, one prompt after the other
+        return [generate(model, p, p.size(0) + m, temperature=temperature, top_k=top_k, eos_id=eos_id,
+                         use_graph=use_graph, rng=SamplerRNG(device, seeds[i]) if sampling else None)
+                for i, (p, m) in enumerate(zip(prompts, budgets))]
+    if sampling and not graph_sampling(model, temperature, top_k):
+        raise NotImplementedError("generate_continuous: sampling runs on the device sampler only (temperature > 0 "
+                                  f"with top_k in [1, {ops.MAX_TOP_K}] over bf16 logits)")
+    model._batch_check(B)  # before any launch
+    if not model.transformer.h[0].attn.batch_fusable(model.transformer.wte.weight.dtype):
+        raise NotImplementedError("generate_continuous needs the batched decode attention launch (head_size == "
+                                  "rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group, bf16 activations)")
+    kv = model.transformer.h[0].attn.kv_cache
+    if kv is None or kv.k.size(0) < B:
+        model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.cache_dtype)
+    from lit_gpt.runtime import SlotDecodeGraph
+
+    ex = SlotDecodeGraph(model, B, chunk=sched.chunk, temperature=temperature, top_k=top_k, use_graph=use_graph)
+    firsts: List[Optional[torch.Tensor]] = [None] * n
+    while not sched.done:
+        while (fill := sched.next_fill()) is not None:  # the single path's prefill (next_token), on the free slot
+            b, i = fill
+            prompt, T = prompts[i], prompts[i].size(0)
+            logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=b)
+            firsts[i] = sample(logits, temperature=temperature, top_k=top_k,
+                               rng=SamplerRNG(device, seeds[i]) if sampling else None).to(dtype=prompt.dtype).clone()
+            if sched.start(b):
+                ex.fill(b, firsts[i], T)
+        if sched.done:
+            break
+        n_steps = sched.next_launch()
+        history = ex.run(n_steps, sched.uniforms(n_steps) if sampling else None)
+        for b in sched.consume(history):
+            ex.release(b)
+    return [torch.cat([p, f, torch.tensor(t, dtype=p.dtype, device=device)])
+            for p, f, t in zip(prompts, firsts, sched.results())]
+
+
 def _check_collectives() -> None:
     """Under tensor parallelism with the xGMI all-reduce: raise (on every rank) if any decode all-reduce of this
     run gave up waiting for a peer — its logits were summed from partial data (lit_gpt/comm.py check_errors)."""
@@ -378,7 +444,7 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
          checkpoint_dir: Path = Path("checkpoints/stabilityai/stablelm-base-alpha-3b"),
          quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
          synthetic: Optional[str] = None, prompt_len: int = 16, batch_size: int = 1,
-         kv_cache: str = "bf16") -> None:
+         kv_cache: str = "bf16", prompts_file: Optional[Path] = None) -> None:
     precision = precision or "bf16-true"
     if not 1 <= batch_size <= MAX_BATCH:
         raise NotImplementedError(f"--batch_size {batch_size}: the batched decode runs 1..{MAX_BATCH} sequences")
@@ -387,11 +453,18 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
     dtype = torch.float32 if precision == "32-true" else torch.bfloat16
     device = torch.device("cuda", torch.cuda.current_device())
     tokenizer = None
+    lines = None
+    if prompts_file is not None:  # one prompt per line (--synthetic: one prompt length per line)
+        lines = [ln.strip() for ln in Path(prompts_file).read_text().splitlines() if ln.strip()]
+        if not lines:
+            raise ValueError(f"--prompts_file {prompts_file}: no prompts")
     if synthetic is not None:
         config = Config.from_name(synthetic)
         checkpoint_path = None
         g = torch.Generator(device="cpu").manual_seed(1234)
-        encoded = torch.randint(0, config.vocab_size, (prompt_len,), generator=g, dtype=torch.int32).to(device)
+        lens = [prompt_len] if lines is None else [int(ln) for ln in lines]
+        many = [torch.randint(0, config.vocab_size, (n,), generator=g, dtype=torch.int32).to(device) for n in lens]
+        encoded = many[0]
     else:
         from lit_gpt.tokenizer import Tokenizer
         from lit_gpt.utils import check_valid_checkpoint_dir
@@ -400,8 +473,9 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
         config = Config.from_json(checkpoint_dir / "lit_config.json")
         checkpoint_path = checkpoint_dir / "lit_model.pth"
         tokenizer = Tokenizer(checkpoint_dir)
-        encoded = tokenizer.encode(prompt, device=device)
-    prompt_length = encoded.size(0)
+        many = [tokenizer.encode(ln, device=device) for ln in (lines if lines is not None else [prompt])]
+        encoded = many[0]
+    prompt_length = encoded.size(0) if lines is None else max(e.size(0) for e in many)
     max_returned_tokens = prompt_length + max_new_tokens
     print(f"Loading model {str(checkpoint_path or synthetic)!r} with {config.__dict__}", file=sys.stderr)
     t0 = time.perf_counter()
@@ -411,6 +485,21 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
     print(f"Time to load the model weights: {time.perf_counter() - t0:.02f} seconds.", file=sys.stderr)
     torch.manual_seed(1234)
     eos_id = tokenizer.eos_id if tokenizer is not None else None
+    if lines is not None:
+        # --prompts_file: every prompt through --batch_size slots (generate_continuous), completions in file order
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys = generate_continuous(model, many, max_new_tokens, batch_size=batch_size, temperature=temperature,
+                                 top_k=top_k, eos_id=eos_id)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        for y in ys:
+            print(tokenizer.decode(y) if tokenizer is not None else y.tolist())
+        tokens_generated = sum(y.size(0) - e.size(0) for y, e in zip(ys, many))
+        print(f"Time for inference of {len(many)} prompts through {min(batch_size, len(many))} slots: {t:.02f} sec "
+              f"total, {tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
+        print(f"Memory used: {torch.cuda.max_memory_allocated() / 1e9:.02f} GB", file=sys.stderr)
+        return
     for i in range(0, num_samples if batch_size > 1 else 0, batch_size):
         # --batch_size B: the samples B at a time, decoded together (generate_batch; each its own sampler seed)
         nb = min(batch_size, num_samples - i)
@@ -456,13 +545,16 @@ def _cli(argv=None) -> None:
     p.add_argument("--prompt_len", type=int, default=16)
     p.add_argument("--batch_size", type=int, default=1,
                    help="decode the samples this many at a time (1..4) through generate_batch")
+    p.add_argument("--prompts_file", type=Path, default=None,
+                   help="one prompt per line (with --synthetic: one prompt length per line); all of them run through "
+                        "--batch_size slots with continuous batching (generate_continuous)")
     p.add_argument("--kv_cache", default="bf16", choices=sorted(KV_CACHE_DTYPES),
                    help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per row (0.516 x the bytes)")
     a = p.parse_args(argv)
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,
          compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, batch_size=a.batch_size,
-         kv_cache=a.kv_cache)
+         kv_cache=a.kv_cache, prompts_file=a.prompts_file)
 
 
 if __name__ == "__main__":

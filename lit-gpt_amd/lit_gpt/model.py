@@ -92,7 +92,7 @@ class GPT(nn.Module):
 
     def forward(self, idx: torch.Tensor, input_pos: Optional[torch.Tensor] = None, *,
                 last_token_only: bool = False, embedded: Optional[torch.Tensor] = None,
-                hidden_only: bool = False, kv_slot: int = 0) -> torch.Tensor:
+                hidden_only: bool = False, kv_slot: int = 0, active: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(B=1, T) ids -> (1, T, padded_vocab) logits; ``last_token_only`` computes only the last row (1, 1, V)
         — all that ``generate`` samples from (generate/base.py:31). ``embedded`` (T * n_embd bf16) is
         ``transformer.wte(idx)`` already gathered — by the previous decode step's ``ops.argmax_embed`` in
@@ -103,7 +103,8 @@ class GPT(nn.Module):
         (B <= MAX_BATCH = 4, T) with a KV cache is the batched form (``_forward_batch``): T > 1 runs each row as the
         B = 1 prefill on slot b at the shared ``input_pos`` (T,); T = 1 is one batched decode step, ``input_pos`` (1,)
         shared or (B,) / (B, 1) one position per sequence, ``embedded`` (B * n_embd). Row b has the bits of the B = 1
-        call on that sequence."""
+        call on that sequence. ``active`` (B,) int32 on the device (batched decode step only, B >= 1): a row flagged 0 is
+        idle — its cache slot is left untouched and its logits are not meaningful."""
         B, T = idx.shape
         if self.max_seq_length < T:
             raise ValueError(f"Cannot forward sequence of length {T}, max seq length is only {self.max_seq_length}.")
@@ -111,8 +112,8 @@ class GPT(nn.Module):
             raise TypeError("You need to call `gpt.set_kv_cache()`")
         if not idx.is_cuda:
             _gpu_only("GPT.forward")
-        if B != 1:
-            return self._forward_batch(idx, input_pos, last_token_only, embedded, hidden_only)
+        if B != 1 or active is not None:  # (a one-slot engine, B = 1 with ``active``, is a batched step of one row)
+            return self._forward_batch(idx, input_pos, last_token_only, embedded, hidden_only, active)
         cos, sin = self._rope_tables()
         if input_pos is not None:
             input_pos = input_pos.to(device=idx.device, dtype=torch.int64).contiguous()
@@ -219,9 +220,10 @@ class GPT(nn.Module):
         ln = self.transformer.ln_f
         return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps, rows=True).view(M, -1)
 
-    def _forward_batch(self, idx, input_pos, last_token_only, embedded, hidden_only) -> torch.Tensor:
+    def _forward_batch(self, idx, input_pos, last_token_only, embedded, hidden_only, active=None) -> torch.Tensor:
         """The B > 1 forms of ``forward`` (its docstring). T = 1 per block: the rows qkv GEMV with norm_1 fused, the
-        one-sequence decode attention once per sequence on its cache slot, the rows out-projection + residual, the
+        decode attention of every sequence on its own cache slot (one batch launch, ``CausalSelfAttention.decode_rows``;
+        ``active`` flags idle rows), the rows out-projection + residual, the
         rows SwiGLU pair with norm_2 fused, the rows down-projection + residual; then ln_f fused into the rows
         lm_head. Every launch is serial on the current stream, so the step captures as one unbranched HIP graph."""
         B, T = idx.shape
@@ -233,8 +235,8 @@ class GPT(nn.Module):
             raise ValueError(f"batch size {B} needs set_kv_cache(batch_size >= {B})")
         input_pos = input_pos.to(device=idx.device, dtype=torch.int64)
         if T > 1:  # the reference's shared positions: each row is the B = 1 prefill on its slot
-            if embedded is not None:
-                raise ValueError("embedded: one token per sequence (T = 1) only")
+            if embedded is not None or active is not None:
+                raise ValueError("embedded / active: one token per sequence (T = 1) only")
             return torch.cat([self.forward(idx[b:b + 1], input_pos, last_token_only=last_token_only,
                                            hidden_only=hidden_only, kv_slot=b) for b in range(B)])
         if input_pos.numel() == 1:
@@ -252,8 +254,10 @@ class GPT(nn.Module):
             x = embedded.view(B, C)
         else:
             x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(B, C)
+        if active is not None and (active.numel() != B or active.dtype != torch.int32 or active.device != idx.device):
+            raise ValueError(f"active must hold {B} int32 flags on the model's device")
         for block in self.transformer.h:
-            x = block.decode_rows(x, cos, sin, pos)
+            x = block.decode_rows(x, cos, sin, pos) if active is None else block.decode_rows(x, cos, sin, pos, active)
         if hidden_only:
             return x.view(B, 1, C)
         ln = self.transformer.ln_f
@@ -319,10 +323,15 @@ class Block(nn.Module):
         self.mlp = config.mlp_class(config)
         self.config = config
 
-    def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                    active: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One batched decode step (GPT._forward_batch has checked the block): x (B, C), one token of each of B
-        sequences at ``pos`` (B,), on the multi-row GEMVs; row b has the bits of ``forward`` on that sequence."""
-        x = self.attn.decode_rows(x, cos, sin, pos, norm=self.norm_1, residual=x)
+        sequences at ``pos`` (B,), on the multi-row GEMVs; row b has the bits of ``forward`` on that sequence.
+        ``active`` (B,) int32: rows flagged 0 are idle in the attention (``CausalSelfAttention.decode_rows``)."""
+        if active is None:
+            x = self.attn.decode_rows(x, cos, sin, pos, norm=self.norm_1, residual=x)
+        else:
+            x = self.attn.decode_rows(x, cos, sin, pos, norm=self.norm_1, residual=x, active=active)
         g = quantize.swiglu(self.mlp.fc_1, self.mlp.fc_2, x, self.norm_2, rows=True)
         return _lin(self.mlp.proj, g, residual=x, rows=True)
 
@@ -488,18 +497,49 @@ class CausalSelfAttention(nn.Module):
         kd, vd = ops.kv8_dequantize(cache, out=kv.scratch)
         return ops.attention(q, kd, vd, pos, H, G, hs, scale, 1, out=out)
 
+    def batch_fusable(self, dtype: torch.dtype) -> bool:
+        """Whether ``ops.attention_decode_batch`` covers this module: the fused decode form's geometry, bf16."""
+        c = self.config
+        return (self.fuse_decode and ops.decode_fusable(c.head_size, c.rope_n_elem)
+                and c.n_head // c.n_query_groups in (1, 2, 4, 8) and dtype == torch.bfloat16)
+
     def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, *,
-                    norm: "RMSNorm", residual: torch.Tensor) -> torch.Tensor:
+                    norm: "RMSNorm", residual: torch.Tensor, active: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Batched decode step: x (B, C), one token of each of B sequences at ``pos`` (B,). The qkv and the
         out-projection run once for all rows (multi-row GEMVs); attention cannot share anything across sequences
-        (each has its own K / V), so the one-sequence decode attention runs once per sequence on row b of qkv and
-        cache slot b, all through the one ``AttentionWorkspace`` (serial launches; its counters re-arm)."""
+        (each has its own K / V): on the fused decode form's geometry it is ONE ``ops.attention_decode_batch`` launch
+        whose row b is the one-sequence launch on row b of qkv and cache slot b (``batch_attention``; the split count
+        is the one-sequence step's, the bits of y depend on it), otherwise the one-sequence decode attention once per
+        sequence, all through the one ``AttentionWorkspace`` (serial launches; its counters re-arm). ``active`` (B,)
+        int32 marks idle rows (0): their cache slot is untouched and their y is zero — the batch launch only."""
         c = self.config
+        H, G, hs = c.n_head, c.n_query_groups, c.head_size
         B = x.size(0)
         kv = self.kv_cache
         qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
         if not kv.fp8 and kv.k.dtype != qkv.dtype:
             kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
+        fusable = self.batch_fusable(qkv.dtype)
+        if active is not None and not fusable:
+            raise NotImplementedError("idle rows (active) need the batched decode attention launch: head_size == "
+                                      "rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group, bf16 activations")
+        if fusable and (batch_attention or active is not None):
+            dev = qkv.device
+            n_splits = ops.decode_splits(G, H // G, hs, kv.k.size(-2))
+            wss = self.__dict__.setdefault("_batch_ws", {})
+            ws = wss.get(B)
+            if ws is None or ws.key != (B, H, G, hs, n_splits) or ws.counters.device != dev:
+                ws = wss[B] = ops.AttentionWorkspace(B, H, G, hs, n_splits, dev)
+            cos = cos.to(device=dev, dtype=torch.float32).contiguous()
+            sin = sin.to(device=dev, dtype=torch.float32).contiguous()
+            if kv.fp8:
+                y = ops.attention_decode_batch_kv8(qkv, (kv.k, kv.v, kv.k_scale, kv.v_scale), pos, cos, sin, H, G, hs,
+                                                   c.rope_n_elem, 1.0 / math.sqrt(hs), n_splits, workspace=ws,
+                                                   active=active)
+            else:
+                y = ops.attention_decode_batch(qkv, kv.k, kv.v, pos, cos, sin, H, G, hs, c.rope_n_elem,
+                                               1.0 / math.sqrt(hs), n_splits, workspace=ws, active=active)
+            return _lin(self.proj, y, residual=residual, rows=True)
         y = torch.empty(B, c.n_head * c.head_size, dtype=qkv.dtype, device=qkv.device)
         for b in range(B):
             p = pos[b:b + 1]
@@ -599,6 +639,11 @@ class LLaMAMLP(nn.Module):
         out = _lin(self.proj, g, residual=residual, reduce=reduce)
         return out.view(*lead, -1)
 
+
+# batched decode step: one ops.attention_decode_batch launch per block for all B sequences; False (LGA_BATCH_ATTN=0)
+# keeps the one-sequence decode attention once per sequence (bit-identical; tools/batch_decode.py and the tests A/B
+# the two). A step with idle rows (``active``) always takes the batch launch.
+batch_attention = os.environ.get("LGA_BATCH_ATTN", "1") != "0"
 
 # decode routing through the fused gate + route launch (lga_moe_gate_route); False keeps lga_q4_gemv + lga_moe_route
 # (tests A/B the two)

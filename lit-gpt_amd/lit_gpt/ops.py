@@ -79,6 +79,10 @@ SIGNATURES = {
                                        _P],
     "lga_attention_decode_window_kv8": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F,
                                         _P],
+    "lga_attention_decode_batch": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, ctypes.c_longlong, _P, _I, _I, _I, _I,
+                                   _I, _I, _F, _P],
+    "lga_attention_decode_batch_kv8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, ctypes.c_longlong,
+                                       ctypes.c_longlong, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "lga_kv8_rope_append": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lga_kv8_dequantize": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_spec_accept": [_P, _I, _I, _P, _P, _P, _P, _P],
@@ -778,6 +782,82 @@ def attention_decode_window_kv8(qkv, cache, pos0, cos, sin, n_head, n_query_grou
         _dev(qkv, "qkv", torch.bfloat16), *ptrs, _dev(pos0, "pos0", torch.int64), _dev(cos, "cos", torch.float32),
         _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, M, n_head,
         n_query_groups, head_size, rope_n_elem, cache[0].shape[-2], n_splits, float(scale), _stream()))
+    return y
+
+
+MAX_BATCH_ROWS = 8  # sequences per lga_attention_decode_batch launch (the rows GEMVs' MAX_GEMV_ROWS)
+
+
+def _batch_args(name, qkv, k_cache, pos, n_head, n_query_groups, head_size, n_splits, workspace, active, out):
+    """The checks the two batch forms share; returns (B, y, ws, cnt, active pointer)."""
+    B = qkv.shape[0]
+    if qkv.dim() != 2 or not 1 <= B <= MAX_BATCH_ROWS:
+        raise ValueError(f"{name}: qkv must be (B, (H + 2G) * hs) with 1 <= B <= {MAX_BATCH_ROWS}, got "
+                         f"{tuple(qkv.shape)}")
+    if qkv.shape[1] != (n_head + 2 * n_query_groups) * head_size:
+        raise ValueError(f"{name}: qkv rows must hold (H + 2G) * hs values")
+    if k_cache.dim() != 4 or k_cache.shape[0] < B or k_cache.shape[1] != n_query_groups:
+        raise ValueError(f"{name}: the caches are the whole (slots >= B, G, max_seq, hs) tensors, got "
+                         f"{tuple(k_cache.shape)} for B = {B}")
+    if pos.numel() != B:
+        raise ValueError(f"{name}: pos holds one position per sequence ({B}), got {tuple(pos.shape)}")
+    if active is not None and (active.numel() != B or active.dtype != torch.int32):
+        raise ValueError(f"{name}: active must hold {B} int32 flags")
+    y = out if out is not None else torch.empty(B, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
+    if y.numel() != B * n_head * head_size:
+        raise ValueError(f"{name}: out must hold (B, H * hs) values")
+    if n_splits > 1:
+        if workspace is None:
+            raise ValueError(f"{name}: split attention needs an AttentionWorkspace(B, ...)")
+        if workspace.key != (B, n_head, n_query_groups, head_size, n_splits):
+            raise ValueError(f"{name}: workspace built for {workspace.key}, the call needs "
+                             f"{(B, n_head, n_query_groups, head_size, n_splits)}")
+        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
+    else:
+        ws = cnt = None
+    return B, y, ws, cnt, _opt(active, "active", torch.int32)
+
+
+def attention_decode_batch(qkv, k_cache, v_cache, pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem,
+                           scale, n_splits=1, workspace: Optional[AttentionWorkspace] = None, active=None, out=None):
+    """One decode token of each of B = qkv.shape[0] (1..8) sequences in ONE launch. ``k_cache`` / ``v_cache`` are the
+    whole (slots, G, max_seq, hs) tensors, row b owns slot b and sits at ``pos[b]`` (cache and rope position, (B,)
+    int64 read on the device). y (B, H*hs) and slot b end bit-identical to ``attention_decode_fused`` on that row and
+    slot with the same ``n_splits``. ``active`` (B,) int32: a row with active[b] == 0 is idle (y[b] = 0, slot b
+    untouched); None runs every row."""
+    name = "attention_decode_batch"
+    B, y, ws, cnt, act = _batch_args(name, qkv, k_cache, pos, n_head, n_query_groups, head_size, n_splits, workspace,
+                                     active, out)
+    if v_cache.shape != k_cache.shape:
+        raise ValueError(f"{name}: k_cache and v_cache must have one shape")
+    _check(load_library().lga_attention_decode_batch(
+        _dev(qkv, "qkv", torch.bfloat16), _dev(k_cache, "k_cache", torch.bfloat16),
+        _dev(v_cache, "v_cache", torch.bfloat16), _dev(pos, "pos", torch.int64), _dev(pos, "pos", torch.int64),
+        _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16),
+        ws, cnt, B, k_cache.stride(0), act, n_head, n_query_groups, head_size, rope_n_elem, k_cache.shape[-2],
+        n_splits, float(scale), _stream()))
+    return y
+
+
+def attention_decode_batch_kv8(qkv, cache, pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale,
+                               n_splits=1, workspace: Optional[AttentionWorkspace] = None, active=None, out=None):
+    """``attention_decode_batch`` over an fp8 cache: ``cache`` is the whole (k codes, v codes, k scales, v scales),
+    codes (slots, G, max_seq, 128) uint8 and scales (slots, G, max_seq) fp32. Row b's y, codes and scales are
+    bit-identical to ``attention_decode_fused_kv8`` on that row and slot with the same ``n_splits``."""
+    name = "attention_decode_batch_kv8"
+    kc, vc, ks, vs = cache
+    B, y, ws, cnt, act = _batch_args(name, qkv, kc, pos, n_head, n_query_groups, head_size, n_splits, workspace,
+                                     active, out)
+    if kc.shape != vc.shape or kc.shape[-1] != 128 or ks.shape != kc.shape[:3] or vs.shape != ks.shape:
+        raise ValueError(f"{name}: an fp8 batch cache is codes (slots, G, max_seq, 128) uint8 x 2 and scales (slots, "
+                         f"G, max_seq) fp32 x 2, got {tuple(kc.shape)}, {tuple(vc.shape)}, {tuple(ks.shape)}, "
+                         f"{tuple(vs.shape)}")
+    _check(load_library().lga_attention_decode_batch_kv8(
+        _dev(qkv, "qkv", torch.bfloat16), _dev(kc, "k_codes", torch.uint8), _dev(vc, "v_codes", torch.uint8),
+        _dev(ks, "k_scale", torch.float32), _dev(vs, "v_scale", torch.float32), _dev(pos, "pos", torch.int64),
+        _dev(pos, "pos", torch.int64), _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32), cos.shape[0],
+        _dev(y, "y", torch.bfloat16), ws, cnt, B, kc.stride(0), ks.stride(0), act, n_head, n_query_groups, head_size,
+        rope_n_elem, kc.shape[-2], n_splits, float(scale), _stream()))
     return y
 
 

@@ -263,3 +263,99 @@ class BatchDecodeGraph:
             raise RuntimeError("BatchDecodeGraph was built with chunk=1 or without graphs")
         self.chunk_graph.replay()
         return self.history
+
+
+class SlotDecodeGraph:
+    """The step executor of continuous batching (generate.base.generate_continuous): ``BatchDecodeGraph`` whose B rows
+    are *slots* that sequences enter and leave between launches while the others' state stays on the device.
+    Device-resident ``token`` (B,), ``pos`` (B,), ``x_emb`` (B, C) and ``history`` (chunk, B) as there, plus ``active``
+    (B,) int32 — an idle slot's attention rows do nothing (``ops.attention_decode_batch``), its cache slot stays as it
+    is — and ``uniforms`` (chunk, B) fp32: under sampling, step s samples row b with ``uniforms[s, b]``, which the
+    host writes before each launch (``ops.sampler_uniform(seed_b, draws_b + s)``), so a slot's seed changes with its
+    sequence without recapturing. One graph for a step and one for ``chunk`` steps, captured once after the first
+    launch has run eagerly; every launch is on one stream, the graphs are chains without branches."""
+
+    def __init__(self, model, B: int, chunk: int = 1, *, temperature: float = 0.0, top_k: Optional[int] = None,
+                 use_graph: bool = True) -> None:
+        wte = model.transformer.wte.weight
+        dev = wte.device
+        if not (wte.is_cuda and wte.dtype == torch.bfloat16 and wte.is_contiguous() and wte.shape[1] % 8 == 0):
+            raise NotImplementedError("batched decode needs a contiguous bf16 embedding table with n_embd % 8 == 0")
+        self.temperature, self.top_k = float(temperature), top_k
+        if self.temperature > 0.0 and (top_k is None or not 1 <= top_k <= ops.MAX_TOP_K):
+            raise ValueError("SlotDecodeGraph: sampling needs top_k in [1, 1024]")
+        self.model, self.B, self.use_graph = model, B, use_graph
+        self.chunk = max(1, int(chunk))
+        self.token = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.pos = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.x_emb = torch.zeros(B, wte.shape[1], dtype=torch.bfloat16, device=dev)
+        self.history = torch.zeros(self.chunk, B, dtype=torch.int64, device=dev)
+        self.active = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.uniforms = torch.full((self.chunk, B), 0.5, dtype=torch.float32, device=dev)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.chunk_graph: Optional[torch.cuda.CUDAGraph] = None
+        self._captured = False
+
+    def fill(self, b: int, token: torch.Tensor, pos: int) -> None:
+        """Sequence enters slot b: its newest token (a one-element device tensor) at position ``pos``. Stream-ordered
+        device writes; the captured graphs read the same buffers."""
+        self.token[b:b + 1].copy_(token.reshape(1))
+        self.pos[b:b + 1].fill_(int(pos))
+        ops.embedding(self.token[b:b + 1], self.model.transformer.wte.weight, out=self.x_emb[b:b + 1])
+        self.active[b:b + 1].fill_(1)
+
+    def release(self, b: int) -> None:
+        """Slot b goes idle: its rows of the following steps leave its cache slot alone."""
+        self.active[b:b + 1].zero_()
+
+    def _step_body(self, s: int) -> None:
+        model, B = self.model, self.B
+        logits = model(self.token.view(B, 1), self.pos, embedded=self.x_emb, active=self.active).view(B, -1)
+        table = model.transformer.wte.weight
+        for b in range(B):
+            out = self.history[s, b:b + 1]
+            if self.temperature > 0.0:
+                ops.sample_topk(logits[b], self.top_k, self.temperature, uniform=self.uniforms[s, b:b + 1],
+                                out_idx=out, token_out=self.token[b:b + 1], pos_inout=self.pos[b:b + 1], table=table,
+                                emb_out=self.x_emb[b])
+            else:
+                ops.argmax_embed(logits[b], table, self.x_emb[b], out_idx=out, token_out=self.token[b:b + 1],
+                                 pos_inout=self.pos[b:b + 1])
+
+    def _capture(self) -> None:
+        torch.cuda.synchronize(self.token.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._step_body(0)
+        self.graph = g
+        if self.chunk > 1:
+            gc = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gc):
+                for s in range(self.chunk):
+                    self._step_body(s)
+            self.chunk_graph = gc
+
+    def run(self, n_steps: int, uniforms=None):
+        """One launch of ``n_steps`` (1 or ``chunk``) decode steps of every slot. ``uniforms``: the (n_steps, B) draws
+        under sampling, written to the device ahead of the launch. Returns the launch's tokens as n_steps lists of B
+        ints — the launch's one device -> host read."""
+        if n_steps not in (1, self.chunk):
+            raise ValueError(f"SlotDecodeGraph: a launch runs 1 or {self.chunk} steps, not {n_steps}")
+        if self.temperature > 0.0:
+            if uniforms is None or len(uniforms) != n_steps:
+                raise ValueError("SlotDecodeGraph: sampling needs the launch's (n_steps, B) uniforms")
+            self.uniforms[:n_steps].copy_(torch.tensor(uniforms, dtype=torch.float32))
+        if not self._captured:  # the first launch is real and eager; then the graphs are captured
+            for s in range(n_steps):
+                self._step_body(s)
+            if self.use_graph:
+                self._capture()
+            self._captured = True
+        elif not self.use_graph:
+            for s in range(n_steps):
+                self._step_body(s)
+        elif n_steps == 1:
+            self.graph.replay()
+        else:
+            self.chunk_graph.replay()
+        return self.history[:n_steps].tolist()
