@@ -433,6 +433,23 @@ int lga_spec_accept_sample(const void* logits, int M, int n, int top_k, float te
                            unsigned long long seed, unsigned long long* counter, const int32_t* window,
                            int32_t* sampled, int32_t* out, int32_t* token_inout, int64_t* pos_inout,
                            lga_stream_t stream);
+/* Nucleus (top-p) sampling in ONE launch, on top of the top-k set (top_k 1..1024) or over the whole vocabulary
+ * (top_k == 0). Candidates C and p as lga_sample_topk computes them over C; w = trunc(p 2^30), W = sum_C w;
+ * target = clamp(ceil((double)top_p (double)W), 1, W); a value class (equal logit value, -0 == +0) is in the nucleus N
+ * iff the weight of the candidates above it is < target (classes enter whole, in descending value); the token is the
+ * first index of N whose running integer sum of w reaches floor((double)u (double)W') + 1, W' = sum_N w. top_p in
+ * (0, 1]. u, seed / counter, the bookkeeping and the embedding gather as lga_sample_topk. Optional outputs (tests), in
+ * index order over C: kept_out (|C| int32, top_k > 0 only), probs_out (|C| bf16; n entries at top_k == 0),
+ * nucleus_out (|C| bytes, 1 inside N). NaN logits and candidate sets whose maximum is -inf are outside the contract. */
+int lga_sample_nucleus(const void* logits, int n, int top_k, float top_p, float temperature, const float* uniform,
+                       unsigned long long seed, unsigned long long* counter, int64_t* out_idx, int32_t* token_out,
+                       int64_t* pos_inout, const void* table, int n_embd, int vocab, void* emb_out, int32_t* kept_out,
+                       void* probs_out, uint8_t* nucleus_out, lga_stream_t stream);
+/* lga_spec_accept_sample with each row drawn by lga_sample_nucleus at top_k (0: none) / top_p / temperature. */
+int lga_spec_accept_sample_nucleus(const void* logits, int M, int n, int top_k, float top_p, float temperature,
+                                   const float* uniform, unsigned long long seed, unsigned long long* counter,
+                                   const int32_t* window, int32_t* sampled, int32_t* out, int32_t* token_inout,
+                                   int64_t* pos_inout, lga_stream_t stream);
 
 /* -- fp32 forward (the reference's --precision 32-true, generate/base.py:132; BASELINE config 1 pythia-160m fp32):
  *    float32 weights and activations, no bf16 rounding; plumbing-sized kernels (csrc/fp32.hip) -------------- */

@@ -25,24 +25,26 @@ wd = Path(__file__).parent.parent.resolve()
 if str(wd) not in sys.path:
     sys.path.append(str(wd))
 
-from generate.base import SamplerRNG, build_model, graph_sampling, next_token  # noqa: E402
+from generate.base import (SamplerRNG, build_model, check_top_p, graph_sampling, next_token,  # noqa: E402
+                           top_k_arg)
 from lit_gpt import GPT, Config  # noqa: E402
 
 
 def _tokens(model: GPT, prompt: torch.Tensor, n: int, temperature: float, top_k: Optional[int],
-            use_graph: bool) -> Iterator[torch.Tensor]:
+            use_graph: bool, top_p: float = 1.0) -> Iterator[torch.Tensor]:
     """Up to ``n`` new tokens, one at a time: prefill at arange(T), then single-token steps."""
+    tp = {"top_p": top_p} if top_p < 1.0 and temperature > 0.0 else {}
     T = prompt.size(0)
     rng = SamplerRNG(prompt.device) if temperature > 0.0 else None
     token = next_token(model, torch.arange(0, T, device=prompt.device), prompt.view(1, -1),
-                       temperature=temperature, top_k=top_k, rng=rng).clone()
+                       temperature=temperature, top_k=top_k, rng=rng, **tp).clone()
     yield token
     if n <= 1:
         return
-    if use_graph and graph_sampling(model, temperature, top_k):
+    if use_graph and graph_sampling(model, temperature, top_k, **tp):
         from lit_gpt.runtime import DecodeGraph
 
-        dg = DecodeGraph(model, token, T, temperature=temperature, top_k=top_k, rng=rng)
+        dg = DecodeGraph(model, token, T, temperature=temperature, top_k=top_k, rng=rng, **tp)
         yield dg.token.view(-1)[:1].clone()
         for _ in range(n - 2):
             yield dg.step().view(-1)[:1].clone()
@@ -50,7 +52,7 @@ def _tokens(model: GPT, prompt: torch.Tensor, n: int, temperature: float, top_k:
     input_pos = torch.tensor([T], device=prompt.device)
     for _ in range(n - 1):
         token = next_token(model, input_pos, token.view(1, -1), temperature=temperature, top_k=top_k,
-                           rng=rng).clone()
+                           rng=rng, **tp).clone()
         yield token
         input_pos = input_pos.add_(1)
 
@@ -58,18 +60,22 @@ def _tokens(model: GPT, prompt: torch.Tensor, n: int, temperature: float, top_k:
 @torch.inference_mode()
 def generate(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, stop_tokens: Tuple[List[int], ...] = (),
-             use_graph: bool = True) -> Iterator[torch.Tensor]:
+             use_graph: bool = True, top_p: float = 1.0) -> Iterator[torch.Tensor]:
     """Continue ``prompt`` (shape (T,)) and yield the new tokens as they become safe to emit (reference
     :23-68): stop as soon as the generated tail equals one of ``stop_tokens``, never yielding that tail."""
     T = prompt.size(0)
     assert max_returned_tokens > T
+    if top_p != 1.0:  # (0, 1]; below 1 on the device sampler only (generate/base.py check_top_p)
+        check_top_p("chat generate", top_p, temperature, top_k, model.transformer.wte.weight.dtype,
+                    model.config.padded_vocab_size)
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     buffer_length = max((len(st) for st in stop_tokens), default=1)
     yield_i = 0
     tokens: List[torch.Tensor] = []
     ids: List[int] = []
-    for t, token in enumerate(_tokens(model, prompt, max_returned_tokens - T, temperature, top_k, use_graph), 1):
+    for t, token in enumerate(_tokens(model, prompt, max_returned_tokens - T, temperature, top_k, use_graph,
+                                      *((top_p,) if top_p < 1.0 else ())), 1):
         tokens.append(token)
         ids.append(int(token))
         if any(len(st) <= len(ids) and ids[-len(st):] == list(st) for st in stop_tokens):
@@ -133,7 +139,7 @@ def prompt_config(checkpoint_dir: Path, tokenizer) -> Tuple[str, Tuple[List[int]
 def main(*, top_k: Optional[int] = 200, temperature: float = 0.8,
          checkpoint_dir: Path = Path("checkpoints/meta-llama/Llama-2-7b-chat-hf"),
          quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
-         kv_cache: str = "bf16") -> None:
+         kv_cache: str = "bf16", top_p: float = 1.0) -> None:
     precision = precision or "bf16-true"
     if precision != "bf16-true":
         raise NotImplementedError("the MI355X path computes in bf16 (precision bf16-true)")
@@ -158,7 +164,7 @@ def main(*, top_k: Optional[int] = 200, temperature: float = 0.8,
             break
         encoded = tokenizer.encode(system_prompt.format(prompt=prompt), device=device)
         y = generate(model, encoded, model.max_seq_length, temperature=temperature, top_k=top_k,
-                     stop_tokens=stop_tokens)
+                     stop_tokens=stop_tokens, **({"top_p": top_p} if top_p < 1.0 else {}))
         print(">> Reply: ", end="")
         t0 = time.perf_counter()
         n = decode(tokenizer, y)
@@ -171,7 +177,8 @@ def main(*, top_k: Optional[int] = 200, temperature: float = 0.8,
 
 def _cli(argv=None) -> None:
     p = argparse.ArgumentParser(description="Starts a conversation with a tuned GPT model.")
-    p.add_argument("--top_k", type=int, default=200)
+    p.add_argument("--top_k", type=top_k_arg, default=200, help="an integer, or 'none'")
+    p.add_argument("--top_p", type=float, default=1.0, help="nucleus sampling (generate/base.py --top_p)")
     p.add_argument("--temperature", type=float, default=0.8)
     p.add_argument("--checkpoint_dir", type=Path, default=Path("checkpoints/meta-llama/Llama-2-7b-chat-hf"))
     p.add_argument("--quantize", default=None)
@@ -181,7 +188,7 @@ def _cli(argv=None) -> None:
                    help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per row (0.516 x the bytes)")
     a = p.parse_args(argv)
     main(top_k=a.top_k, temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize,
-         precision=a.precision, compile=a.compile, kv_cache=a.kv_cache)
+         precision=a.precision, compile=a.compile, kv_cache=a.kv_cache, top_p=a.top_p)
 
 
 if __name__ == "__main__":

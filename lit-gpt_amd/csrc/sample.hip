@@ -556,6 +556,314 @@ __global__ void __launch_bounds__(64) window_sample_accept_kernel(const int32_t*
   if (counter) *counter += (unsigned long long)(a + 1);
 }
 
+// ---- nucleus (top-p) sampling, on top of the top-k set or over the whole vocabulary ----------------
+// Defined over integers so that no result depends on a summation order:
+//   C  = the top-k set as topk_sample_row keeps it (k > 0), or every index (k == 0)
+//   p  = bf16(exp(x - max x) / sum), x = bf16(v / T), over C (the fp32 sum is the one order-dependent quantity)
+//   w  = trunc(p 2^30), W = sum_C w (< 2^31: u32 adds, exact in any order)
+//   target = clamp(ceil(double(top_p) double(W)), 1, W); a value class (equal order_key) is in the nucleus N iff the
+//   weight of the classes above it is < target — classes enter whole, in descending value, until top_p is reached
+//   tau = floor(double(u) double(W')) + 1, W' = sum_N w; the token is the first index of N whose running sum of w
+//   reaches tau (no second softmax: N is sampled in proportion to p).
+// Same layout as topk_sample_row: 1024 threads, the logits staged once in LDS, thread t owns [t EPT, t EPT + EPT).
+// The keys are read from the LDS copy in every pass and the weights are recomputed from it, so LDS holds the row
+// (128 KiB at EPT 64), one set of per-wave histograms (16 KiB) and a few words. The threshold key (the smallest key
+// whose class is in N) comes from a weighted MSD radix select: a 256-bin histogram of w by the key's high byte, the
+// bin where the descending running weight first reaches target, then the same on the low byte inside that bin.
+// kept_out (|C| int32, k > 0 only), probs_out (|C| bf16) and nucleus_out (|C| bytes) are in index order, for tests.
+template <int EPT>
+__device__ __forceinline__ int nucleus_sample_row(const uint16_t* __restrict__ logits, int n, int k, float top_p,
+                                                  float temperature, float u0, int32_t* __restrict__ kept_out,
+                                                  uint16_t* __restrict__ probs_out,
+                                                  uint8_t* __restrict__ nucleus_out) {
+  constexpr int NT = 1024, NW = 16;
+  static_assert(EPT % 8 == 0 && EPT <= 64, "16-B LDS reads, one 64-bit candidate mask per thread");
+  __shared__ __attribute__((aligned(16))) uint16_t sx[NT * EPT];
+  __shared__ unsigned hist[NW][256];
+  __shared__ unsigned wsum[NW], wmax_s[NW];
+  __shared__ float red[NW];
+  __shared__ unsigned s_sel, s_before, s_found;
+  __shared__ int s_tok;
+  __shared__ float s_u;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (((uintptr_t)logits & 3) == 0) {
+    for (int i2 = t; i2 < NT * EPT / 2; i2 += NT) {
+      const int i = 2 * i2;
+      uint32_t v = 0xFF80FF80u;
+      if (i + 1 < n) v = ((const uint32_t*)logits)[i2];
+      else if (i < n) v = (uint32_t)logits[i] | 0xFF800000u;
+      ((uint32_t*)sx)[i2] = v;
+    }
+  } else {
+    for (int i = t; i < NT * EPT; i += NT) sx[i] = i < n ? logits[i] : (uint16_t)0xFF80u;
+  }
+  for (int i = t; i < NW * 256; i += NT) (&hist[0][0])[i] = 0;
+  if (t == 0) {
+    s_tok = 0;
+    s_u = u0;
+  }
+  __syncthreads();
+  LGA_STRACE(8);
+  // f(e, bits) over this thread's elements in index order, eight per 16-B LDS read
+  auto for_each = [&](auto f) {
+    const uint4* src = (const uint4*)(sx + t * EPT);
+    // (EPT 64: a rolled chunk loop; unrolled, the weight passes' 64 exponentials spill to scratch)
+    constexpr int kChunks = EPT == 64 ? 1 : EPT / 8;
+#pragma unroll kChunks
+    for (int c = 0; c < EPT / 8; ++c) {
+      const uint4 v = src[c];
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        f(8 * c + 2 * h, (uint16_t)(w[h] & 0xFFFFu));
+        f(8 * c + 2 * h + 1, (uint16_t)(w[h] >> 16));
+      }
+    }
+  };
+  auto clear_hist = [&]() {
+    for (int i = t; i < NW * 256; i += NT) (&hist[0][0])[i] = 0;
+    __syncthreads();
+  };
+  // after a histogram pass: bin t's total over the waves (c) and the inclusive running total from bin 0 (pre), for
+  // t < 256; returns the total of all bins
+  auto hist_scan = [&](unsigned& c, unsigned& pre) -> unsigned {
+    __syncthreads();
+    c = 0;
+    if (t < 256)
+#pragma unroll
+      for (int w = 0; w < NW; ++w) c += hist[w][t];
+    const unsigned inc = wave_incl_scan(c, lane);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    pre = inc;
+    for (int w = 0; w < wave && w < 4; ++w) pre += wsum[w];
+    return wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  };
+  // the bin where the running total first reaches `need` (sel) and the total before it; false when no bin does
+  auto find = [&](unsigned c, unsigned pre, unsigned need, unsigned& sel, unsigned& before) -> bool {
+    if (t == 0) s_found = 0;
+    __syncthreads();
+    if (t < 256 && pre >= need && pre - c < need) {
+      s_sel = t;
+      s_before = pre - c;
+      s_found = 1;
+    }
+    __syncthreads();
+    sel = s_sel;
+    before = s_before;
+    const bool found = s_found != 0;
+    __syncthreads();
+    return found;
+  };
+  // exclusive block prefix sum in thread order; `total` to every thread
+  auto block_scan = [&](unsigned v, unsigned& total) -> unsigned {
+    const unsigned inc = wave_incl_scan(v, lane);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned before = 0, all = 0;
+    for (int w = 0; w < NW; ++w) {
+      before += w < wave ? wsum[w] : 0u;
+      all += wsum[w];
+    }
+    __syncthreads();
+    total = all;
+    return before + inc - v;
+  };
+  // ---- the largest key: the softmax's maximum (x is monotone in v), and the top-k fast path's anchor ----
+  unsigned kmax;
+  {
+    unsigned m = 0;
+    for_each([&](int, uint16_t b) { m = max(m, order_key(b)); });
+    m = wave_max_u(m);
+    if (lane == 0) wmax_s[wave] = m;
+    __syncthreads();
+    kmax = wmax_s[0];
+    for (int w = 1; w < NW; ++w) kmax = max(kmax, wmax_s[w]);
+  }
+  // ---- the candidates C, one bit per owned element ----
+  unsigned long long cmask = 0;
+  if (k > 0) {  // topk_sample_row's kept set: the k-th largest key, ties at it lowest index first
+    k = min(k, n);
+    unsigned c, pre, sel, before, kth, gt;
+    for_each([&](int, uint16_t b) {
+      const unsigned d = kmax - order_key(b);
+      if (d < 256u) atomicAdd(&hist[wave][d], 1u);
+    });
+    hist_scan(c, pre);
+    if (find(c, pre, (unsigned)k, sel, before)) {
+      kth = kmax - sel;
+      gt = before;
+    } else {
+      clear_hist();
+      for_each([&](int, uint16_t b) { atomicAdd(&hist[wave][255u - (order_key(b) >> 8)], 1u); });
+      hist_scan(c, pre);
+      find(c, pre, (unsigned)k, sel, before);
+      const unsigned hi = 255u - sel, above = before;
+      clear_hist();
+      for_each([&](int, uint16_t b) {
+        const unsigned kk = order_key(b);
+        if ((kk >> 8) == hi) atomicAdd(&hist[wave][255u - (kk & 255u)], 1u);
+      });
+      hist_scan(c, pre);
+      find(c, pre, (unsigned)k - above, sel, before);
+      kth = (hi << 8) | (255u - sel);
+      gt = above + before;
+    }
+    const unsigned need = (unsigned)k - gt;
+    unsigned ties = 0, total;
+    for_each([&](int, uint16_t b) { ties += order_key(b) == kth; });
+    unsigned tie_seen = block_scan(ties, total);
+    for_each([&](int e, uint16_t b) {
+      const unsigned kk = order_key(b);
+      bool keep = kk > kth;
+      if (kk == kth) keep = tie_seen++ < need;
+      if (keep && t * EPT + e < n) cmask |= 1ull << e;
+    });
+    clear_hist();
+  } else {
+    for_each([&](int e, uint16_t) {
+      if (t * EPT + e < n) cmask |= 1ull << e;
+    });
+  }
+  LGA_STRACE(9);
+  // ---- softmax over C: the maximum is the largest key's x; the fp32 sum in thread / wave order ----
+  const uint16_t maxbits = (uint16_t)((kmax & 0x8000u) ? (kmax & 0x7FFFu) : (~kmax & 0xFFFFu));
+  const float xm = round_bf(bf2f(maxbits) / temperature);
+  float sum;
+  {
+    float s = 0.0f;
+    for_each([&](int e, uint16_t b) {
+      if ((cmask >> e) & 1) s += expf(round_bf(bf2f(b) / temperature) - xm);
+    });
+    s = wave_sum(s);
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    sum = 0.0f;
+    for (int w = 0; w < NW; ++w) sum += red[w];
+  }
+  auto prob = [&](uint16_t b) -> float { return round_bf(expf(round_bf(bf2f(b) / temperature) - xm) / sum); };
+  // w = trunc(p 2^30). Below x - max = -22, exp < 2^-31 and sum >= 1 (the maximum's own term), so p < 2^-30 and
+  // w = 0 without the exponential
+  auto weight = [&](uint16_t b) -> unsigned {
+    const float d = round_bf(bf2f(b) / temperature) - xm;
+    if (!(d >= -22.0f)) return 0u;
+    return (unsigned)(round_bf(expf(d) / sum) * 0x1.0p30f);
+  };
+  LGA_STRACE(10);
+  // ---- the threshold key: weighted radix select, high byte then low byte ----
+  unsigned kstar;
+  {
+    unsigned c, pre, sel, before;
+    for_each([&](int e, uint16_t b) {
+      if ((cmask >> e) & 1) {
+        const unsigned w = weight(b);
+        if (w) atomicAdd(&hist[wave][255u - (order_key(b) >> 8)], w);
+      }
+    });
+    const unsigned W = hist_scan(c, pre);
+    const double tg = ceil((double)top_p * (double)W);
+    const unsigned target = tg < 1.0 ? 1u : (tg > (double)W ? W : (unsigned)tg);
+    find(c, pre, target, sel, before);
+    const unsigned hi = 255u - sel, rest = target - before;
+    LGA_STRACE(13);
+    clear_hist();
+    for_each([&](int e, uint16_t b) {
+      const unsigned kk = order_key(b);
+      if (((cmask >> e) & 1) && (kk >> 8) == hi) {
+        const unsigned w = weight(b);
+        if (w) atomicAdd(&hist[wave][255u - (kk & 255u)], w);
+      }
+    });
+    hist_scan(c, pre);
+    find(c, pre, rest, sel, before);
+    kstar = (hi << 8) | (255u - sel);
+  }
+  LGA_STRACE(11);
+  // ---- the draw: an integer block scan of the nucleus weights in index order, then the tau search ----
+  unsigned mine = 0, Wn;
+  for_each([&](int e, uint16_t b) {
+    if (((cmask >> e) & 1) && order_key(b) >= kstar) mine += weight(b);
+  });
+  const unsigned before = block_scan(mine, Wn);
+  unsigned long long tau = (unsigned long long)floor((double)s_u * (double)Wn) + 1ull;
+  if (tau > Wn) tau = Wn;
+  if (mine && before < tau && tau <= (unsigned long long)before + mine) {
+    unsigned run = before;
+    int tok = -1;
+    for_each([&](int e, uint16_t b) {
+      if (((cmask >> e) & 1) && order_key(b) >= kstar) {
+        const unsigned w = weight(b);
+        if (tok < 0 && w && run + w >= tau) tok = t * EPT + e;
+        run += w;
+      }
+    });
+    if (tok >= 0) s_tok = tok;
+  }
+  if (kept_out || probs_out || nucleus_out) {  // (tests) the candidates' indices, probabilities and flags
+    unsigned total;
+    unsigned pos = block_scan((unsigned)__popcll(cmask), total);
+    const unsigned room = (unsigned)(k > 0 ? k : n);  // what the callers' buffers hold
+    for_each([&](int e, uint16_t b) {
+      if (((cmask >> e) & 1) && pos < room) {
+        if (kept_out) kept_out[pos] = t * EPT + e;
+        if (probs_out) probs_out[pos] = f2bf(prob(b));
+        if (nucleus_out) nucleus_out[pos] = order_key(b) >= kstar;
+        ++pos;
+      }
+    });
+  }
+  __syncthreads();
+  LGA_STRACE(12);
+  return s_tok;
+}
+
+template <int EPT>
+__global__ void __launch_bounds__(1024) kernel_sample_nucleus(
+    const uint16_t* __restrict__ logits, int n, int k, float top_p, float temperature,
+    const float* __restrict__ uniform, unsigned long long seed, unsigned long long* __restrict__ counter,
+    int64_t* __restrict__ out_idx, int32_t* __restrict__ token_out, int64_t* __restrict__ pos_inout,
+    const uint16_t* __restrict__ table, int C, int V, uint16_t* __restrict__ emb_out, int32_t* __restrict__ kept_out,
+    uint16_t* __restrict__ probs_out, uint8_t* __restrict__ nucleus_out) {
+  constexpr int NT = 1024;
+  const int t = threadIdx.x;
+  float u0 = 0.0f;
+  if (t == 0) {
+    if (uniform) {
+      u0 = *uniform;
+    } else {
+      const unsigned long long cn = *counter;
+      *counter = cn + 1;
+      u0 = draw_uniform(seed, cn);
+    }
+  }
+  const int pick = nucleus_sample_row<EPT>(logits, n, k, top_p, temperature, u0, kept_out, probs_out, nucleus_out);
+  if (t == 0) {
+    if (out_idx) *out_idx = pick;
+    if (token_out) *token_out = pick;
+    if (pos_inout) *pos_inout += 1;
+  }
+  if (emb_out) {
+    const long id = min(max(pick, 0), V - 1);
+    const uint4* src = (const uint4*)(table + (size_t)id * C);
+    for (int i = t; i < C / 8; i += NT) ((uint4*)emb_out)[i] = src[i];
+  }
+}
+
+// one workgroup per window row, as window_sample_kernel: row r draws kernel_sample_nucleus's token for its logits
+// under uniform[r] or draw number *counter + r; window_sample_accept_kernel follows unchanged
+template <int EPT>
+__global__ void __launch_bounds__(1024) kernel_window_sample_nucleus(
+    const uint16_t* __restrict__ logits, int n, int k, float top_p, float temperature,
+    const float* __restrict__ uniform, unsigned long long seed, const unsigned long long* __restrict__ counter,
+    int32_t* __restrict__ sampled) {
+  const int r = blockIdx.x;
+  float u0 = 0.0f;
+  if (threadIdx.x == 0) u0 = uniform ? uniform[r] : draw_uniform(seed, *counter + (unsigned long long)r);
+  const int pick =
+      nucleus_sample_row<EPT>(logits + (size_t)r * n, n, k, top_p, temperature, u0, nullptr, nullptr, nullptr);
+  if (threadIdx.x == 0) sampled[r] = pick;
+}
+
 }  // namespace lga
 
 int lga::preload_sample() {
@@ -563,7 +871,10 @@ int lga::preload_sample() {
          lga::preload(lga::topk_sample_kernel<16>) + lga::preload(lga::topk_sample_kernel<32>) +
          lga::preload(lga::topk_sample_kernel<64>) + lga::preload(lga::window_sample_kernel<16>) +
          lga::preload(lga::window_sample_kernel<32>) + lga::preload(lga::window_sample_kernel<64>) +
-         lga::preload(lga::window_sample_accept_kernel);
+         lga::preload(lga::window_sample_accept_kernel) + lga::preload(lga::kernel_sample_nucleus<16>) +
+         lga::preload(lga::kernel_sample_nucleus<32>) + lga::preload(lga::kernel_sample_nucleus<64>) +
+         lga::preload(lga::kernel_window_sample_nucleus<16>) + lga::preload(lga::kernel_window_sample_nucleus<32>) +
+         lga::preload(lga::kernel_window_sample_nucleus<64>);
 }
 
 extern "C" int lga_argmax(const void* logits, int n, int64_t* out_idx, int32_t* token_out, int64_t* pos_inout,
@@ -651,6 +962,55 @@ extern "C" int lga_spec_accept_sample(const void* logits, int M, int n, int top_
   else LGA_WINDOW_TOPK(64);
 #undef LGA_WINDOW_TOPK
   // with explicit uniforms the counter is left alone, as lga_sample_topk leaves it
+  lga::window_sample_accept_kernel<<<1, 64, 0, stream>>>(sampled, M, window, out, token_inout, pos_inout,
+                                                         uniform ? nullptr : counter);
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_sample_nucleus(const void* logits, int n, int top_k, float top_p, float temperature,
+                                  const float* uniform, unsigned long long seed, unsigned long long* counter,
+                                  int64_t* out_idx, int32_t* token_out, int64_t* pos_inout, const void* table,
+                                  int n_embd, int vocab, void* emb_out, int32_t* kept_out, void* probs_out,
+                                  uint8_t* nucleus_out, hipStream_t stream) {
+  LGA_CHECK_ARG(logits && n > 0 && n <= 1024 * 64, "lga_sample_nucleus: needs 0 < n <= 65536 logits");
+  LGA_CHECK_ARG(top_k >= 0 && top_k <= lga::kMaxTopK, "lga_sample_nucleus: top_k must be 0 (none) or in [1, 1024]");
+  LGA_CHECK_ARG(top_p > 0.0f && top_p <= 1.0f, "lga_sample_nucleus: top_p must be in (0, 1]");
+  LGA_CHECK_ARG(temperature > 0.0f, "lga_sample_nucleus: temperature must be > 0 (0 is lga_argmax)");
+  LGA_CHECK_ARG(uniform || counter, "lga_sample_nucleus: needs a uniform or an RNG counter");
+  LGA_CHECK_ARG(!emb_out || (table && n_embd > 0 && n_embd % 8 == 0 && vocab > 0 && ((uintptr_t)table & 15) == 0 &&
+                             ((uintptr_t)emb_out & 15) == 0),
+                "lga_sample_nucleus: the embedding gather needs a 16-B aligned table and emb_out, n_embd % 8 == 0");
+#define LGA_NUCLEUS(EPT)                                                                                           \
+  lga::kernel_sample_nucleus<EPT><<<1, 1024, 0, stream>>>(                                                         \
+      (const uint16_t*)logits, n, top_k, top_p, temperature, uniform, seed, counter, out_idx, token_out, pos_inout, \
+      (const uint16_t*)table, n_embd, vocab, (uint16_t*)emb_out, kept_out, (uint16_t*)probs_out, nucleus_out)
+  if (n <= 1024 * 16) LGA_NUCLEUS(16);
+  else if (n <= 1024 * 32) LGA_NUCLEUS(32);
+  else LGA_NUCLEUS(64);
+#undef LGA_NUCLEUS
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_spec_accept_sample_nucleus(const void* logits, int M, int n, int top_k, float top_p,
+                                              float temperature, const float* uniform, unsigned long long seed,
+                                              unsigned long long* counter, const int32_t* window, int32_t* sampled,
+                                              int32_t* out, int32_t* token_inout, int64_t* pos_inout,
+                                              hipStream_t stream) {
+  LGA_CHECK_ARG(logits && window && out && sampled, "lga_spec_accept_sample_nucleus: bad arguments");
+  LGA_CHECK_ARG(M >= 1 && M <= lga::kMaxWindow, "lga_spec_accept_sample_nucleus: M must be in [1, 8]");
+  LGA_CHECK_ARG(n > 0 && n <= 1024 * 64, "lga_spec_accept_sample_nucleus: needs 0 < n <= 65536 logits per row");
+  LGA_CHECK_ARG(top_k >= 0 && top_k <= lga::kMaxTopK,
+                "lga_spec_accept_sample_nucleus: top_k must be 0 (none) or in [1, 1024]");
+  LGA_CHECK_ARG(top_p > 0.0f && top_p <= 1.0f, "lga_spec_accept_sample_nucleus: top_p must be in (0, 1]");
+  LGA_CHECK_ARG(temperature > 0.0f, "lga_spec_accept_sample_nucleus: temperature must be > 0 (0 is lga_spec_accept)");
+  LGA_CHECK_ARG(uniform || counter, "lga_spec_accept_sample_nucleus: needs uniforms or an RNG counter");
+#define LGA_WINDOW_NUCLEUS(EPT)                                                                                     \
+  lga::kernel_window_sample_nucleus<EPT><<<M, 1024, 0, stream>>>((const uint16_t*)logits, n, top_k, top_p,          \
+                                                                 temperature, uniform, seed, counter, sampled)
+  if (n <= 1024 * 16) LGA_WINDOW_NUCLEUS(16);
+  else if (n <= 1024 * 32) LGA_WINDOW_NUCLEUS(32);
+  else LGA_WINDOW_NUCLEUS(64);
+#undef LGA_WINDOW_NUCLEUS
   lga::window_sample_accept_kernel<<<1, 64, 0, stream>>>(sampled, M, window, out, token_inout, pos_inout,
                                                          uniform ? nullptr : counter);
   LGA_LAUNCH_RETURN();

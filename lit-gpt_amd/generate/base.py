@@ -9,6 +9,8 @@ short) and ``main`` (:96-187) with the same flags and the same stderr timing lin
     top-k + softmax + inverse-CDF sampler on the device — the role ``--compile`` (CUDA graphs) plays in the
     reference; the sampler's uniforms come from a counter-based RNG seeded from torch's generator, so a seed
     reproduces a run but not the reference's exact torch.multinomial draws;
+  * ``--top_p P`` (``top_p=P``; not in the reference) adds nucleus sampling on the device for ``0 < P < 1``, over
+    the top-k set or, with ``--top_k none``, the whole vocabulary (ops.sample_nucleus; no torch fallback);
   * ``--quantize`` takes this build's formats (int4-g128, nf4 / bnb.nf4 / bnb.nf4-dq, bnb.fp4 / bnb.fp4-dq, bnb.int8);
     without it the Linears
     stay bf16 ``nn.Linear`` (BASELINE config 2) and run on the bf16 GEMV / GEMM kernels;
@@ -48,24 +50,51 @@ class SamplerRNG:
         self.counter = torch.zeros(1, dtype=torch.int64, device=device)
 
 
-def device_sampling(temperature: float, top_k: Optional[int], dtype: torch.dtype, vocab: int = 0) -> bool:
+def device_sampling(temperature: float, top_k: Optional[int], dtype: torch.dtype, vocab: int = 0,
+                    top_p: float = 1.0) -> bool:
     """Whether ``sample`` at this setting runs as the one-launch HIP sampler (ops.sample_topk): temperature > 0 with
     top_k in [1, 1024] over bf16 logits of at most 65536 entries — the reference's defaults (top_k 200,
-    temperature 0.8) included."""
+    temperature 0.8) included. With 0 < top_p < 1 (ops.sample_nucleus) top_k may also be None."""
+    if 0.0 < top_p < 1.0:
+        return (temperature > 0.0 and (top_k is None or 1 <= top_k <= ops.MAX_TOP_K) and dtype == torch.bfloat16
+                and vocab <= ops.MAX_SAMPLE_VOCAB)
     return (temperature > 0.0 and top_k is not None and 1 <= top_k <= ops.MAX_TOP_K and dtype == torch.bfloat16
             and vocab <= ops.MAX_SAMPLE_VOCAB)
 
 
+def _top_p_kw(top_p: float) -> dict:
+    """``top_p`` as a keyword for the callees, passed on only when it is in effect (< 1)."""
+    return {"top_p": top_p} if top_p < 1.0 else {}
+
+
+def check_top_p(who: str, top_p: float, temperature: float, top_k: Optional[int], dtype: torch.dtype,
+                vocab: int) -> None:
+    """``top_p`` must lie in (0, 1]; below 1 (and at temperature > 0) it runs on the device sampler only: there is no
+    torch fallback for top-p."""
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"{who}: top_p must be in (0, 1], got {top_p}")
+    if top_p < 1.0 and temperature > 0.0 and not device_sampling(temperature, top_k, dtype, vocab, top_p):
+        raise NotImplementedError(f"{who}: top_p < 1 runs on the device sampler only: bf16 logits, a vocabulary of at "
+                                  f"most {ops.MAX_SAMPLE_VOCAB} and top_k None or in [1, {ops.MAX_TOP_K}]")
+
+
 def sample(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None,
-           rng: Optional[SamplerRNG] = None) -> torch.Tensor:
+           rng: Optional[SamplerRNG] = None, top_p: float = 1.0) -> torch.Tensor:
     """logits (1, T, V) on the GPU -> (1,) token (generate/base.py:30-41). Greedy runs the HIP argmax (lowest index
     on ties; top-k cannot change the arg-max); temperature > 0 with top_k <= 1024 over bf16 logits runs the HIP
     top-k + softmax + inverse-CDF sampler in one launch (``rng`` carries its RNG state; a fresh one is drawn from
-    torch's generator when omitted); other settings follow the reference's torch ops, softmax in the logits' dtype."""
+    torch's generator when omitted); other settings follow the reference's torch ops, softmax in the logits' dtype.
+    ``top_p`` < 1 adds nucleus sampling (ops.sample_nucleus, one launch, top_k None or <= 1024 over bf16 logits; no
+    torch fallback); at temperature 0 it changes nothing, the arg-max is always in the nucleus."""
     logits = logits[0, -1]
+    check_top_p("sample", top_p, temperature, top_k, logits.dtype, logits.size(-1))
     if not logits.is_cuda:
         raise RuntimeError("sample: logits must be on the GPU (this build has no CPU path)")
     if temperature > 0.0:
+        if top_p < 1.0:
+            rng = rng if rng is not None else SamplerRNG(logits.device)
+            return ops.sample_nucleus(logits.contiguous(), top_k, top_p, temperature, seed=rng.seed,
+                                      counter=rng.counter)
         if device_sampling(temperature, top_k, logits.dtype, logits.size(-1)):
             rng = rng if rng is not None else SamplerRNG(logits.device)
             return ops.sample_topk(logits.contiguous(), top_k, temperature, seed=rng.seed, counter=rng.counter)
@@ -82,11 +111,15 @@ def next_token(model: GPT, input_pos: torch.Tensor, x: torch.Tensor, **kwargs: A
     return sample(logits, **kwargs).to(dtype=x.dtype)
 
 
-def graph_sampling(model: GPT, temperature: float, top_k: Optional[int]) -> bool:
+def graph_sampling(model: GPT, temperature: float, top_k: Optional[int], top_p: float = 1.0) -> bool:
     """Whether decode steps at this setting run as captured HIP graphs (lit_gpt/runtime.py DecodeGraph): greedy, or
     the device sampler (``device_sampling``) over the model's bf16 logits."""
     wte = model.transformer.wte.weight
-    return temperature == 0.0 or device_sampling(temperature, top_k, wte.dtype, model.config.padded_vocab_size)
+    return temperature == 0.0 or device_sampling(temperature, top_k, wte.dtype, model.config.padded_vocab_size, top_p)
+
+
+def _check_model_top_p(who: str, model: GPT, top_p: float, temperature: float, top_k: Optional[int]) -> None:
+    check_top_p(who, top_p, temperature, top_k, model.transformer.wte.weight.dtype, model.config.padded_vocab_size)
 
 
 DECODE_CHUNK = 8  # greedy decode steps per graph launch (lit_gpt/runtime.py DecodeGraph.steps)
@@ -95,30 +128,36 @@ DECODE_CHUNK = 8  # greedy decode steps per graph launch (lit_gpt/runtime.py Dec
 @torch.inference_mode()
 def generate(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, *, temperature: float = 1.0,
              top_k: Optional[int] = None, eos_id: Optional[int] = None, use_graph: bool = True,
-             rng: Optional[SamplerRNG] = None) -> torch.Tensor:
+             rng: Optional[SamplerRNG] = None, top_p: float = 1.0) -> torch.Tensor:
     """Takes a conditioning sequence (prompt, shape (T,)) and continues it; returns (T + new,) ids. ``rng``: the
-    device sampler's state to draw from (a fresh one seeded from torch's generator when omitted)."""
+    device sampler's state to draw from (a fresh one seeded from torch's generator when omitted). ``top_p`` < 1:
+    nucleus sampling on the device (``sample``)."""
     T = prompt.size(0)
     assert max_returned_tokens > T
+    if top_p != 1.0:
+        _check_model_top_p("generate", model, top_p, temperature, top_k)
+        if temperature == 0.0:
+            top_p = 1.0  # greedy: top-p cannot change the arg-max
+    tp = _top_p_kw(top_p)
     if model.max_seq_length < max_returned_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {max_returned_tokens - 1}")
     device = prompt.device
     tokens = [prompt]
     rng = (rng or SamplerRNG(device)) if temperature > 0.0 else None
     token = next_token(model, torch.arange(0, T, device=device), prompt.view(1, -1), temperature=temperature,
-                       top_k=top_k, rng=rng).clone()
+                       top_k=top_k, rng=rng, **tp).clone()
     tokens.append(token)
     n_steps = max_returned_tokens - T - 1
     if n_steps <= 0:
         return torch.cat(tokens)
-    if use_graph and graph_sampling(model, temperature, top_k):
+    if use_graph and graph_sampling(model, temperature, top_k, **tp):
         from lit_gpt.runtime import DecodeGraph
 
         # (the prefill's token is never tested against eos: the reference's loop only tests the decoded ones,
         # generate/base.py:86-92)
         # runs the first decode step eagerly, then captures the step (and DECODE_CHUNK steps as one graph)
         dg = DecodeGraph(model, token, T, chunk=DECODE_CHUNK if n_steps > DECODE_CHUNK else 1,
-                         temperature=temperature, top_k=top_k, rng=rng)
+                         temperature=temperature, top_k=top_k, rng=rng, **tp)
         out = torch.empty(n_steps, dtype=prompt.dtype, device=device)
         out[0] = dg.token.view(-1)[0]
         produced = 1
@@ -144,7 +183,7 @@ def generate(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, *, temp
     input_pos = torch.tensor([T], device=device)
     for _ in range(n_steps):
         token = next_token(model, input_pos, token.view(1, -1), temperature=temperature, top_k=top_k,
-                           rng=rng).clone()
+                           rng=rng, **tp).clone()
         tokens.append(token)
         if eos_id is not None and int(token) == eos_id:
             break
@@ -192,7 +231,7 @@ def _batch_steps(dg, n_steps: int, eos_id: Optional[int]):
 @torch.inference_mode()
 def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seeds: Optional[List[int]] = None,
-                   use_graph: bool = True) -> List[torch.Tensor]:
+                   use_graph: bool = True, top_p: float = 1.0) -> List[torch.Tensor]:
     """Continue up to MAX_BATCH = 4 prompts (each (T_b,), lengths may differ) by ``max_new_tokens`` tokens each,
     decoding them together: every decode step streams the weights once for all sequences (the multi-row GEMVs; attention runs per
     sequence). Sequence b gets exactly the tokens ``generate`` returns for ``prompts[b]`` alone (under sampling: with
@@ -202,6 +241,11 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
     B = len(prompts)
     if B == 0:
         raise ValueError("generate_batch: no prompts")
+    if top_p != 1.0:
+        _check_model_top_p("generate_batch", model, top_p, temperature, top_k)
+        if temperature == 0.0:
+            top_p = 1.0
+    tp = _top_p_kw(top_p)
     if B > MAX_BATCH:
         raise NotImplementedError(f"generate_batch: {B} prompts; the MI355X batched decode runs at most {MAX_BATCH} "
                                   "sequences per step")
@@ -213,7 +257,7 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
     if model.max_seq_length < longest + max_new_tokens - 1:
         raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= "
                                   f"{longest + max_new_tokens - 1}")
-    if B > 1 and temperature > 0.0 and not graph_sampling(model, temperature, top_k):
+    if B > 1 and temperature > 0.0 and not graph_sampling(model, temperature, top_k, **tp):
         raise NotImplementedError("generate_batch: sampling a batch runs on the device sampler only (temperature > 0 "
                                   f"with top_k in [1, {ops.MAX_TOP_K}] over bf16 logits)")
     device = prompts[0].device
@@ -222,7 +266,7 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
         rngs = [SamplerRNG(device, None if seeds is None else seeds[b]) for b in range(B)]
     if B == 1:
         return [generate(model, prompts[0], prompts[0].size(0) + max_new_tokens, temperature=temperature, top_k=top_k,
-                         eos_id=eos_id, use_graph=use_graph, rng=None if rngs is None else rngs[0])]
+                         eos_id=eos_id, use_graph=use_graph, rng=None if rngs is None else rngs[0], **tp)]
     kv = model.transformer.h[0].attn.kv_cache
     if kv is None or kv.k.size(0) < B:
         model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.cache_dtype)
@@ -231,7 +275,7 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
         T = prompt.size(0)
         logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=b)
         firsts.append(sample(logits, temperature=temperature, top_k=top_k,
-                             rng=None if rngs is None else rngs[b]).to(dtype=prompt.dtype).clone())
+                             rng=None if rngs is None else rngs[b], **tp).to(dtype=prompt.dtype).clone())
     n_steps = max_new_tokens - 1
     if n_steps <= 0:
         return [torch.cat([p, f]) for p, f in zip(prompts, firsts)]
@@ -239,7 +283,7 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
 
     dg = BatchDecodeGraph(model, torch.cat(firsts), [p.size(0) for p in prompts],
                           chunk=DECODE_CHUNK if use_graph and n_steps > DECODE_CHUNK else 1,
-                          temperature=temperature, top_k=top_k, rngs=rngs, use_graph=use_graph)
+                          temperature=temperature, top_k=top_k, rngs=rngs, use_graph=use_graph, **tp)
     out, lengths = _batch_steps(dg, n_steps, eos_id)
     return [torch.cat([p, f, out[:n_b, b].to(p.dtype)]) for b, (p, f, n_b) in enumerate(zip(prompts, firsts, lengths))]
 
@@ -248,7 +292,7 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
 def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens, *, batch_size: int = MAX_BATCH,
                         temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None,
                         seeds: Optional[List[int]] = None, use_graph: bool = True,
-                        chunk: int = DECODE_CHUNK) -> List[torch.Tensor]:
+                        chunk: int = DECODE_CHUNK, top_p: float = 1.0) -> List[torch.Tensor]:
     """Continuous batching: any number of prompts (each (T_i,)) through ``min(batch_size, len(prompts))`` slots of the
     batched decode step. ``max_new_tokens``: an int, or one per prompt. A prompt enters a free slot through the single
     path's prefill; a sequence that met ``eos_id`` or its budget leaves its slot to the next prompt of the queue while
@@ -261,6 +305,11 @@ def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens,
     n = len(prompts)
     if n == 0:
         raise ValueError("generate_continuous: no prompts")
+    if top_p != 1.0:
+        _check_model_top_p("generate_continuous", model, top_p, temperature, top_k)
+        if temperature == 0.0:
+            top_p = 1.0
+    tp = _top_p_kw(top_p)
     if batch_size < 1:
         raise ValueError("generate_continuous: batch_size must be at least 1")
     if batch_size > MAX_BATCH:
@@ -275,9 +324,9 @@ def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens,
     budgets = [s + 1 for s in sched.steps_budget]
     if B == 1:  # one slot: the single path, one prompt after the other
         return [generate(model, p, p.size(0) + m, temperature=temperature, top_k=top_k, eos_id=eos_id,
-                         use_graph=use_graph, rng=SamplerRNG(device, seeds[i]) if sampling else None)
+                         use_graph=use_graph, rng=SamplerRNG(device, seeds[i]) if sampling else None, **tp)
                 for i, (p, m) in enumerate(zip(prompts, budgets))]
-    if sampling and not graph_sampling(model, temperature, top_k):
+    if sampling and not graph_sampling(model, temperature, top_k, **tp):
         raise NotImplementedError("generate_continuous: sampling runs on the device sampler only (temperature > 0 "
                                   f"with top_k in [1, {ops.MAX_TOP_K}] over bf16 logits)")
     model._batch_check(B)  # before any launch
@@ -289,7 +338,8 @@ def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens,
         model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.cache_dtype)
     from lit_gpt.runtime import SlotDecodeGraph
 
-    ex = SlotDecodeGraph(model, B, chunk=sched.chunk, temperature=temperature, top_k=top_k, use_graph=use_graph)
+    ex = SlotDecodeGraph(model, B, chunk=sched.chunk, temperature=temperature, top_k=top_k, use_graph=use_graph,
+                         **tp)
     firsts: List[Optional[torch.Tensor]] = [None] * n
     while not sched.done:
         while (fill := sched.next_fill()) is not None:  # the single path's prefill (next_token), on the free slot
@@ -297,7 +347,8 @@ def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens,
             prompt, T = prompts[i], prompts[i].size(0)
             logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=b)
             firsts[i] = sample(logits, temperature=temperature, top_k=top_k,
-                               rng=SamplerRNG(device, seeds[i]) if sampling else None).to(dtype=prompt.dtype).clone()
+                               rng=SamplerRNG(device, seeds[i]) if sampling else None,
+                               **tp).to(dtype=prompt.dtype).clone()
             if sched.start(b):
                 ex.fill(b, firsts[i], T)
         if sched.done:
@@ -444,8 +495,11 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
          checkpoint_dir: Path = Path("checkpoints/stabilityai/stablelm-base-alpha-3b"),
          quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
          synthetic: Optional[str] = None, prompt_len: int = 16, batch_size: int = 1,
-         kv_cache: str = "bf16", prompts_file: Optional[Path] = None) -> None:
+         kv_cache: str = "bf16", prompts_file: Optional[Path] = None, top_p: float = 1.0) -> None:
     precision = precision or "bf16-true"
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"--top_p must be in (0, 1], got {top_p}")
+    tp = _top_p_kw(top_p)
     if not 1 <= batch_size <= MAX_BATCH:
         raise NotImplementedError(f"--batch_size {batch_size}: the batched decode runs 1..{MAX_BATCH} sequences")
     if precision not in ("bf16-true", "32-true"):
@@ -490,7 +544,7 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ys = generate_continuous(model, many, max_new_tokens, batch_size=batch_size, temperature=temperature,
-                                 top_k=top_k, eos_id=eos_id)
+                                 top_k=top_k, eos_id=eos_id, **tp)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         for y in ys:
@@ -505,7 +559,8 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
         nb = min(batch_size, num_samples - i)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ys = generate_batch(model, [encoded] * nb, max_new_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id)
+        ys = generate_batch(model, [encoded] * nb, max_new_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id,
+                            **tp)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         for block in model.transformer.h:
@@ -518,7 +573,7 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
     for i in range(num_samples if batch_size == 1 else 0):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        y = generate(model, encoded, max_returned_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id)
+        y = generate(model, encoded, max_returned_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id, **tp)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         for block in model.transformer.h:
@@ -530,12 +585,20 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
     print(f"Memory used: {torch.cuda.max_memory_allocated() / 1e9:.02f} GB", file=sys.stderr)
 
 
+def top_k_arg(text: str) -> Optional[int]:
+    """--top_k: an integer, or the word ``none``."""
+    return None if text.strip().lower() == "none" else int(text)
+
+
 def _cli(argv=None) -> None:
     p = argparse.ArgumentParser(description="Generates text samples based on a pre-trained model and tokenizer.")
     p.add_argument("--prompt", default="What food do llamas eat?")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--max_new_tokens", type=int, default=50)
-    p.add_argument("--top_k", type=int, default=200)
+    p.add_argument("--top_k", type=top_k_arg, default=200, help="an integer, or 'none' (with --top_p: the nucleus "
+                   "over the whole vocabulary)")
+    p.add_argument("--top_p", type=float, default=1.0, help="nucleus sampling: the smallest set of most likely "
+                   "tokens whose probability reaches top_p (1.0: off)")
     p.add_argument("--temperature", type=float, default=0.8)
     p.add_argument("--checkpoint_dir", type=Path, default=Path("checkpoints/stabilityai/stablelm-base-alpha-3b"))
     p.add_argument("--quantize", default=None)
@@ -554,7 +617,7 @@ def _cli(argv=None) -> None:
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,
          compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, batch_size=a.batch_size,
-         kv_cache=a.kv_cache, prompts_file=a.prompts_file)
+         kv_cache=a.kv_cache, prompts_file=a.prompts_file, top_p=a.top_p)
 
 
 if __name__ == "__main__":

@@ -32,7 +32,7 @@ wd = Path(__file__).parent.parent.resolve()
 if str(wd) not in sys.path:
     sys.path.append(str(wd))
 
-from generate.base import build_model, generate  # noqa: E402
+from generate.base import build_model, generate, top_k_arg  # noqa: E402
 from lit_gpt import lora  # noqa: E402
 
 lora_r = 8
@@ -69,7 +69,7 @@ def main(prompt: str = "What food do llamas eat?", input: str = "",
          checkpoint_dir: Path = Path("checkpoints/stabilityai/stablelm-base-alpha-3b"),
          quantize: Optional[str] = None, max_new_tokens: int = 100, top_k: Optional[int] = 200,
          temperature: float = 0.8, precision: Optional[str] = None, merge: Optional[bool] = None,
-         synthetic: Optional[str] = None, prompt_len: int = 16) -> List[int]:
+         synthetic: Optional[str] = None, prompt_len: int = 16, top_p: float = 1.0) -> List[int]:
     """Generates a response to an instruction (and optional input) with the adapter of ``lora_path`` on the model of
     ``checkpoint_dir``; returns the token ids (prompt + generated)."""
     precision = precision or "bf16-true"
@@ -127,7 +127,8 @@ def main(prompt: str = "What food do llamas eat?", input: str = "",
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     y = generate(model, encoded, max_returned_tokens, temperature=temperature, top_k=top_k,
-                 eos_id=tokenizer.eos_id if tokenizer is not None else None)
+                 eos_id=tokenizer.eos_id if tokenizer is not None else None,
+                 **({"top_p": top_p} if top_p < 1.0 else {}))
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
     if tokenizer is not None:
@@ -148,7 +149,8 @@ def _cli(argv=None) -> None:
     p.add_argument("--checkpoint_dir", type=Path, default=Path("checkpoints/stabilityai/stablelm-base-alpha-3b"))
     p.add_argument("--quantize", default=None)
     p.add_argument("--max_new_tokens", type=int, default=100)
-    p.add_argument("--top_k", type=int, default=200)
+    p.add_argument("--top_k", type=top_k_arg, default=200, help="an integer, or 'none'")
+    p.add_argument("--top_p", type=float, default=1.0, help="nucleus sampling (generate/base.py --top_p)")
     p.add_argument("--temperature", type=float, default=0.8)
     p.add_argument("--precision", default=None)
     p.add_argument("--merge", action=argparse.BooleanOptionalAction, default=None,
@@ -159,7 +161,7 @@ def _cli(argv=None) -> None:
     p.add_argument("--prompt_len", type=int, default=16)
     a = p.parse_args(argv)
     main(a.prompt, a.input, a.lora_path, a.checkpoint_dir, a.quantize, a.max_new_tokens, a.top_k, a.temperature,
-         a.precision, a.merge, a.synthetic, a.prompt_len)
+         a.precision, a.merge, a.synthetic, a.prompt_len, a.top_p)
 
 
 if __name__ == "__main__":

@@ -168,7 +168,7 @@ def _same(a: torch.device, b: torch.device) -> bool:
 def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_new_tokens: int = 50,
          top_k: Optional[int] = 200, temperature: float = 0.8,
          checkpoint_dir: Path = Path("checkpoints/mistralai/Mistral-7B-Instruct-v0.1"),
-         quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
+         quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False, top_p: float = 1.0,
          synthetic: Optional[str] = None, prompt_len: int = 16, devices: Optional[int] = None) -> None:
     precision = precision or "bf16-true"
     if precision != "bf16-true":
@@ -209,7 +209,8 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         y = generate_base.generate(model, encoded, max_returned_tokens, temperature=temperature, top_k=top_k,
-                                   eos_id=eos_id, use_graph=total_devices == 1)
+                                   eos_id=eos_id, use_graph=total_devices == 1,
+                                   **({"top_p": top_p} if top_p < 1.0 else {}))
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         for block in model.transformer.h:
@@ -226,7 +227,8 @@ def _cli(argv=None) -> None:
     p.add_argument("--prompt", default="What food do llamas eat?")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--max_new_tokens", type=int, default=50)
-    p.add_argument("--top_k", type=int, default=200)
+    p.add_argument("--top_k", type=generate_base.top_k_arg, default=200, help="an integer, or 'none'")
+    p.add_argument("--top_p", type=float, default=1.0, help="nucleus sampling (generate/base.py --top_p)")
     p.add_argument("--temperature", type=float, default=0.8)
     p.add_argument("--checkpoint_dir", type=Path, default=Path("checkpoints/mistralai/Mistral-7B-Instruct-v0.1"))
     p.add_argument("--quantize", default=None)
@@ -238,7 +240,7 @@ def _cli(argv=None) -> None:
     a = p.parse_args(argv)
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,
-         compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, devices=a.devices)
+         compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, devices=a.devices, top_p=a.top_p)
 
 
 if __name__ == "__main__":

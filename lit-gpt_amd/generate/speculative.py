@@ -116,6 +116,7 @@ class ModelDrafter:
         self.valid = 0
         self.buf: Optional[torch.Tensor] = None
         self.sampling = None  # (temperature, top_k, seed) while drafting with the target's uniforms
+        self.top_p = 1.0
         self.rng = None
         self.T = 0
 
@@ -126,9 +127,12 @@ class ModelDrafter:
         if self.model.transformer.wte.weight.device != target.transformer.wte.weight.device:
             raise ValueError("the draft model must sit on the target's device")
 
-    def set_sampling(self, temperature: float, top_k: Optional[int], seed: int) -> None:
-        """The target's sampling setting for the run about to ``begin`` (temperature 0: greedy)."""
-        self.sampling = (float(temperature), int(top_k), int(seed)) if temperature > 0.0 and self.coupled else None
+    def set_sampling(self, temperature: float, top_k: Optional[int], seed: int, top_p: float = 1.0) -> None:
+        """The target's sampling setting for the run about to ``begin`` (temperature 0: greedy). ``top_p`` < 1: the
+        draft model's logits are sampled at the target's ``top_p`` too (``top_k`` may then be None)."""
+        k = None if top_k is None else int(top_k)
+        self.sampling = (float(temperature), k, int(seed)) if temperature > 0.0 and self.coupled else None
+        self.top_p = float(top_p)
 
     def begin(self, prompt: torch.Tensor, first_token: int) -> None:
         m = self.model
@@ -155,6 +159,8 @@ class ModelDrafter:
             kw = {}
             if self.rng is not None:
                 kw = dict(temperature=self.sampling[0], top_k=self.sampling[1], rng=self.rng)
+                if self.top_p < 1.0:
+                    kw["top_p"] = self.top_p
             self.dg = DecodeGraph(self.model, first, pos, **kw)  # runs that step itself, then captures
         else:
             self.dg.reset(token, pos)
@@ -216,7 +222,7 @@ def speculative_rounds(executor, drafter, tokens: List[int], n_steps: int, max_s
 def generate_speculative(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, drafter, *,
                          speculate: int = DEFAULT_SPECULATE, eos_id: Optional[int] = None, use_graph: bool = True,
                          stats: Optional[Dict[str, int]] = None, temperature: float = 0.0,
-                         top_k: Optional[int] = None, rng=None) -> torch.Tensor:
+                         top_k: Optional[int] = None, rng=None, top_p: float = 1.0) -> torch.Tensor:
     """``generate(model, prompt, max_returned_tokens, temperature=0.0, eos_id=eos_id)``, token for token, in fewer
     target passes: each round verifies up to ``speculate`` drafts of ``drafter`` (``NgramDrafter``, ``ModelDrafter``)
     in one window and emits the accepted ones plus the target's next token. The KV cache must be the one ``generate``
@@ -226,15 +232,24 @@ def generate_speculative(model: GPT, prompt: torch.Tensor, max_returned_tokens: 
     With ``temperature > 0`` and ``top_k`` in 1..1024 it returns, token for token, what ``generate(model, prompt,
     max_returned_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id, rng=SamplerRNG(device, seed=s))``
     returns for the seed ``s`` of ``rng`` (a ``generate.base.SamplerRNG``; omitted: seeded from torch's generator, as
-    ``generate`` does). The prefill's token is draw 0 and the n-th generated token draw n."""
-    from generate.base import SamplerRNG, next_token
+    ``generate`` does). The prefill's token is draw 0 and the n-th generated token draw n. With ``top_p`` < 1 the
+    same holds for ``generate(..., top_p=top_p)`` on the device nucleus sampler, and ``top_k`` may be None."""
+    from generate.base import SamplerRNG, check_top_p, next_token
     from lit_gpt import ops
 
     sampling = temperature > 0.0
-    if sampling and top_k is None:
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"generate_speculative: top_p must be in (0, 1], got {top_p}")
+    if not sampling:
+        top_p = 1.0  # greedy: top-p cannot change the arg-max
+    nucleus = top_p < 1.0
+    if nucleus:
+        check_top_p("generate_speculative", top_p, temperature, top_k, model.transformer.wte.weight.dtype,
+                    model.config.padded_vocab_size)
+    if sampling and top_k is None and not nucleus:
         raise NotImplementedError("without top_k generate_speculative is greedy only: speculative sampling runs on "
                                   f"the device top-k sampler (top_k 1..{ops.MAX_TOP_K})")
-    if sampling and not 1 <= top_k <= ops.MAX_TOP_K:
+    if sampling and top_k is not None and not 1 <= top_k <= ops.MAX_TOP_K:
         raise NotImplementedError(f"speculative sampling runs on the device top-k sampler: top_k must be in "
                                   f"1..{ops.MAX_TOP_K}, got {top_k}")
     if not 1 <= speculate <= GPT.MAX_WINDOW - 1:
@@ -249,7 +264,7 @@ def generate_speculative(model: GPT, prompt: torch.Tensor, max_returned_tokens: 
 
     # everything the verify step refuses is refused here, before the prefill
     model._rows_check("speculative decoding")
-    if sampling and not graph_sampling(model, temperature, top_k):
+    if sampling and not nucleus and not graph_sampling(model, temperature, top_k):
         raise NotImplementedError("speculative sampling runs on the device top-k sampler: bf16 logits of at most "
                                   f"{ops.MAX_SAMPLE_VOCAB} entries (this model: {c.padded_vocab_size})")
     if not ops.decode_fusable(c.head_size, c.rope_n_elem) or c.n_head // c.n_query_groups not in (1, 2, 4, 8):
@@ -260,8 +275,10 @@ def generate_speculative(model: GPT, prompt: torch.Tensor, max_returned_tokens: 
     device = prompt.device
     rng = (rng or SamplerRNG(device)) if sampling else None
     if hasattr(drafter, "set_sampling"):
-        drafter.set_sampling(temperature, top_k, rng.seed if sampling else 0)
+        drafter.set_sampling(temperature, top_k, rng.seed if sampling else 0, *((top_p,) if nucleus else ()))
     kw = dict(temperature=temperature, top_k=top_k, rng=rng) if sampling else dict(temperature=0.0)
+    if nucleus:
+        kw["top_p"] = top_p
     token = next_token(model, torch.arange(0, T, device=device), prompt.view(1, -1), **kw).clone()
     n_steps = max_returned_tokens - T - 1
     if n_steps <= 0:
@@ -280,15 +297,19 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
          prompt_len: int = 16, draft: Optional[str] = None, draft_checkpoint_dir: Optional[Path] = None,
          draft_synthetic: Optional[str] = None, draft_quantize: Optional[str] = "int4-g128",
          speculate: int = DEFAULT_SPECULATE, temperature: float = 0.0, top_k: Optional[int] = None,
-         kv_cache: str = "bf16") -> None:
+         kv_cache: str = "bf16", top_p: float = 1.0) -> None:
     """``kv_cache`` is the TARGET's cache format (generate/base.py ``--kv_cache``); a draft model keeps bf16.
-    ``temperature`` > 0 needs ``top_k`` in 1..1024 and prints what generate/base.py prints at that setting."""
+    ``temperature`` > 0 needs ``top_k`` in 1..1024 and prints what generate/base.py prints at that setting; with
+    ``top_p`` < 1 (nucleus sampling) ``top_k`` may be None."""
     from generate.base import build_model
     from lit_gpt import ops
 
     if (precision or "bf16-true") != "bf16-true":
         raise NotImplementedError("speculative decoding runs 4-bit weights under bf16-true")
-    if temperature > 0.0 and (top_k is None or not 1 <= top_k <= ops.MAX_TOP_K):
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"--top_p must be in (0, 1], got {top_p}")
+    if temperature > 0.0 and ((top_k is None and top_p == 1.0) or
+                              (top_k is not None and not 1 <= top_k <= ops.MAX_TOP_K)):
         raise NotImplementedError("without --top_k in 1..1024 generate/speculative.py is greedy only (temperature 0)")
     kinds = [draft is not None, draft_checkpoint_dir is not None, draft_synthetic is not None]
     if sum(kinds) != 1:
@@ -337,7 +358,8 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     y = generate_speculative(model, encoded, max_returned_tokens, drafter, speculate=speculate, eos_id=eos_id,
-                             stats=stats, temperature=temperature, top_k=top_k)
+                             stats=stats, temperature=temperature, top_k=top_k,
+                             **({"top_p": top_p} if top_p < 1.0 else {}))
     torch.cuda.synchronize()
     t = time.perf_counter() - t0
     print(tokenizer.decode(y) if tokenizer is not None else y.tolist())
@@ -348,6 +370,10 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
           f"{stats.get('tokens', 0) / max(1, stats.get('rounds', 0)):.2f} tokens per target pass over "
           f"{stats.get('rounds', 0)} passes", file=sys.stderr)
     print(f"Memory used: {torch.cuda.max_memory_allocated() / 1e9:.02f} GB", file=sys.stderr)
+
+
+def _top_k_arg(text: str) -> Optional[int]:
+    return None if text.strip().lower() == "none" else int(text)
 
 
 def parse_args(argv=None) -> argparse.Namespace:
@@ -362,7 +388,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--precision", default=None)
     p.add_argument("--temperature", type=float, default=0.0,
                    help="0: greedy; > 0 samples as generate/base.py does and needs --top_k")
-    p.add_argument("--top_k", type=int, default=None, help="with --temperature > 0: sample among the top_k (1..1024)")
+    p.add_argument("--top_k", type=_top_k_arg, default=None,
+                   help="with --temperature > 0: sample among the top_k (1..1024); 'none' with --top_p")
+    p.add_argument("--top_p", type=float, default=1.0,
+                   help="with --temperature > 0: nucleus sampling as generate/base.py --top_p (1.0: off)")
     p.add_argument("--synthetic", default=None, help="random-init target of this registered config name")
     p.add_argument("--prompt_len", type=int, default=16)
     p.add_argument("--draft", default=None, choices=["ngram"], help="prompt-lookup drafting on the host")
@@ -380,7 +409,9 @@ def parse_args(argv=None) -> argparse.Namespace:
         p.error(f"--speculate must be in 1..{GPT.MAX_WINDOW - 1}")
     if a.top_k is not None and not 1 <= a.top_k <= 1024:
         p.error("--top_k must be in 1..1024 (the device top-k sampler)")
-    if a.temperature > 0.0 and a.top_k is None:
+    if not 0.0 < a.top_p <= 1.0:
+        p.error("--top_p must be in (0, 1]")
+    if a.temperature > 0.0 and a.top_k is None and a.top_p == 1.0:
         p.error("--temperature > 0 needs --top_k in 1..1024: without it speculative decoding here is greedy only")
     return a
 
@@ -391,7 +422,7 @@ def _cli(argv=None) -> None:
          precision=a.precision, synthetic=a.synthetic, prompt_len=a.prompt_len, draft=a.draft,
          draft_checkpoint_dir=a.draft_checkpoint_dir, draft_synthetic=a.draft_synthetic,
          draft_quantize=a.draft_quantize, speculate=a.speculate, temperature=a.temperature, top_k=a.top_k,
-         kv_cache=a.kv_cache)
+         kv_cache=a.kv_cache, top_p=a.top_p)
 
 
 if __name__ == "__main__":

@@ -140,7 +140,7 @@ def init_distributed(allreduce: Optional[str] = None) -> Fabric:
 def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_new_tokens: int = 50,
          top_k: Optional[int] = 200, temperature: float = 0.8, checkpoint_dir: Path = Path("checkpoints"),
          quantize: Optional[str] = None, precision: Optional[str] = None, synthetic: Optional[str] = None,
-         prompt_len: int = 16) -> None:
+         prompt_len: int = 16, top_p: float = 1.0) -> None:
     fabric = init_distributed()
     device = torch.device("cuda", torch.cuda.current_device())
     if synthetic is not None:
@@ -169,7 +169,8 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         y = generate_base.generate(model, encoded, max_returned, temperature=temperature, top_k=top_k,
-                                   eos_id=None if tokenizer is None else tokenizer.eos_id)
+                                   eos_id=None if tokenizer is None else tokenizer.eos_id,
+                                   **({"top_p": top_p} if top_p < 1.0 else {}))
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         for block in model.transformer.h:
@@ -185,7 +186,8 @@ if __name__ == "__main__":
     p.add_argument("--prompt", default="What food do llamas eat?")
     p.add_argument("--num_samples", type=int, default=1)
     p.add_argument("--max_new_tokens", type=int, default=50)
-    p.add_argument("--top_k", type=int, default=200)
+    p.add_argument("--top_k", type=generate_base.top_k_arg, default=200, help="an integer, or 'none'")
+    p.add_argument("--top_p", type=float, default=1.0, help="nucleus sampling (generate/base.py --top_p)")
     p.add_argument("--temperature", type=float, default=0.8)
     p.add_argument("--checkpoint_dir", type=Path, default=Path("checkpoints"))
     p.add_argument("--quantize", default=None)
@@ -195,4 +197,4 @@ if __name__ == "__main__":
     a = p.parse_args()
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,
-         synthetic=a.synthetic, prompt_len=a.prompt_len)
+         synthetic=a.synthetic, prompt_len=a.prompt_len, top_p=a.top_p)

@@ -123,6 +123,8 @@ SIGNATURES = {
     "lga_argmax_f32": [_P, _I, _P, _P, _P, _P],
     "lga_sample_topk": [_P, _I, _I, _F, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
     "lga_spec_accept_sample": [_P, _I, _I, _I, _F, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _P, _P],
+    "lga_sample_nucleus": [_P, _I, _I, _F, _F, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "lga_spec_accept_sample_nucleus": [_P, _I, _I, _I, _F, _F, _P, ctypes.c_ulonglong, _P, _P, _P, _P, _P, _P, _P],
     "lga_q4_gemv_allreduce": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(_P), _I, _I, _I, _P, _P, _P,
                               _P],
     "lga_q4_gemv_allreduce_tagged": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(_P), _I, _I, _I, _P, _P,
@@ -1128,6 +1130,80 @@ def spec_accept_sample(logits, window, top_k, temperature, *, uniform=None, seed
         raise ValueError("spec_accept_sample: sampled needs one int32 per row")
     _check(load_library().lga_spec_accept_sample(
         lp, M, n, int(top_k), float(temperature), _opt(uniform, "uniform", torch.float32), int(seed) & _U64,
+        _opt(counter, "counter", torch.int64), _dev(window, "window", torch.int32), _dev(tmp, "sampled", torch.int32),
+        _dev(res, "out", torch.int32), _opt(token_inout, "token_inout", torch.int32),
+        _opt(pos_inout, "pos_inout", torch.int64), _stream()))
+    return res
+
+
+def _nucleus_args(name: str, n: int, top_k, top_p, temperature, uniform, counter) -> int:
+    """Shared argument checks of the nucleus ops; returns top_k as the C ABI takes it (None -> 0)."""
+    if not 0 < n <= MAX_SAMPLE_VOCAB:
+        raise ValueError(f"{name}: {n} logits, the sampler takes 1..{MAX_SAMPLE_VOCAB}")
+    if top_k is not None and not 1 <= top_k <= MAX_TOP_K:
+        raise ValueError(f"{name}: top_k must be None or in [1, {MAX_TOP_K}], got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"{name}: top_p must be in (0, 1], got {top_p}")
+    if not temperature > 0.0:
+        raise ValueError(f"{name}: temperature must be > 0 (0 is greedy)")
+    if uniform is None and counter is None:
+        raise ValueError(f"{name}: needs uniform or an RNG counter")
+    return 0 if top_k is None else int(top_k)
+
+
+def sample_nucleus(logits, top_k, top_p, temperature, *, uniform=None, seed=0, counter=None, out_idx=None,
+                   token_out=None, pos_inout=None, table=None, emb_out=None, kept_out=None, probs_out=None,
+                   nucleus_out=None):
+    """Nucleus (top-p) sampling in ONE launch (csrc/sample.hip kernel_sample_nucleus): over the top-k
+    set (``top_k`` 1..1024) or the whole vocabulary (``top_k=None``), the value classes enter in descending order
+    until their integer weight reaches ``top_p`` of the total, and the token is drawn from them in proportion to the
+    bf16 softmax of ``logits / temperature``. ``uniform`` / ``seed`` / ``counter``, the bookkeeping outputs and the
+    embedding gather as ``sample_topk``. ``kept_out`` (int32, top-k form), ``probs_out`` (bf16), ``nucleus_out``
+    (uint8): the candidates in index order, their probabilities and nucleus flags (tests). Returns out_idx."""
+    n = logits.numel()
+    k = _nucleus_args("sample_nucleus", n, top_k, top_p, temperature, uniform, counter)
+    idx = out_idx if out_idx is not None else torch.empty(1, dtype=torch.int64, device=logits.device)
+    V, C = (table.shape if table is not None else (0, 0))
+    if emb_out is not None and (table is None or emb_out.numel() != C):
+        raise ValueError("sample_nucleus: emb_out needs the embedding table and one row of it")
+    cand = min(k, n) if k else n
+    for t, nm in ((kept_out, "kept_out"), (probs_out, "probs_out"), (nucleus_out, "nucleus_out")):
+        if t is not None and t.numel() < cand:
+            raise ValueError(f"sample_nucleus: {nm} needs {cand} entries")
+    if kept_out is not None and not k:
+        raise ValueError("sample_nucleus: kept_out belongs to the top-k form")
+    _check(load_library().lga_sample_nucleus(
+        _dev(logits, "logits", torch.bfloat16), n, k, float(top_p), float(temperature),
+        _opt(uniform, "uniform", torch.float32), int(seed) & _U64, _opt(counter, "counter", torch.int64),
+        _dev(idx, "out_idx", torch.int64), _opt(token_out, "token_out", torch.int32),
+        _opt(pos_inout, "pos_inout", torch.int64), _opt(table, "table", torch.bfloat16), C, V,
+        _opt(emb_out, "emb_out", torch.bfloat16), _opt(kept_out, "kept_out", torch.int32),
+        _opt(probs_out, "probs_out", torch.bfloat16), _opt(nucleus_out, "nucleus_out", torch.uint8), _stream()))
+    return idx
+
+
+def spec_accept_sample_nucleus(logits, window, top_k, top_p, temperature, *, uniform=None, seed=0, counter=None,
+                               out=None, token_inout=None, pos_inout=None, sampled=None):
+    """``spec_accept_sample`` with each row drawn as ``sample_nucleus`` draws it at ``top_k`` (None: the whole
+    vocabulary) / ``top_p`` / ``temperature`` (csrc/sample.hip lga_spec_accept_sample_nucleus)."""
+    if logits.dim() != 2 or not 1 <= logits.shape[0] <= MAX_WINDOW_ROWS:
+        raise ValueError(f"spec_accept_sample_nucleus: logits must be (M, n) with 1 <= M <= {MAX_WINDOW_ROWS}, "
+                         f"got {tuple(logits.shape)}")
+    M, n = logits.shape
+    k = _nucleus_args("spec_accept_sample_nucleus", n, top_k, top_p, temperature, uniform, counter)
+    if window.numel() != M:
+        raise ValueError(f"spec_accept_sample_nucleus: window holds {window.numel()} tokens for {M} rows of logits")
+    if uniform is not None and uniform.numel() != M:
+        raise ValueError(f"spec_accept_sample_nucleus: {uniform.numel()} uniforms for {M} rows of logits")
+    lp = _dev(logits, "logits", torch.bfloat16)
+    res = out if out is not None else torch.empty(M + 1, dtype=torch.int32, device=logits.device)
+    if res.numel() < M + 1:
+        raise ValueError("spec_accept_sample_nucleus: out needs M + 1 int32 values")
+    tmp = sampled if sampled is not None else torch.empty(MAX_WINDOW_ROWS, dtype=torch.int32, device=logits.device)
+    if tmp.numel() < M:
+        raise ValueError("spec_accept_sample_nucleus: sampled needs one int32 per row")
+    _check(load_library().lga_spec_accept_sample_nucleus(
+        lp, M, n, k, float(top_p), float(temperature), _opt(uniform, "uniform", torch.float32), int(seed) & _U64,
         _opt(counter, "counter", torch.int64), _dev(window, "window", torch.int32), _dev(tmp, "sampled", torch.int32),
         _dev(res, "out", torch.int32), _opt(token_inout, "token_inout", torch.int32),
         _opt(pos_inout, "pos_inout", torch.int64), _stream()))

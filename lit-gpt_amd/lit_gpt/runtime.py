@@ -19,20 +19,32 @@ import torch
 
 from lit_gpt import ops, quantize
 
+
+def _sampling_ok(temperature: float, top_k: Optional[int], top_p: float) -> bool:
+    """The device samplers' settings: top_k in [1, 1024] (ops.sample_topk), or, with 0 < top_p < 1, top_k in
+    [1, 1024] or None (ops.sample_nucleus)."""
+    if not 0.0 < top_p <= 1.0:
+        return False
+    if top_k is None:
+        return top_p < 1.0
+    return 1 <= top_k <= ops.MAX_TOP_K
+
 class DecodeGraph:
     def __init__(self, model, first_token: torch.Tensor, first_pos: int, chunk: int = 1, *,
-                 temperature: float = 0.0, top_k: Optional[int] = None, rng=None) -> None:
+                 temperature: float = 0.0, top_k: Optional[int] = None, rng=None, top_p: float = 1.0) -> None:
         """Runs one real decode step eagerly (token ``first_token`` at position ``first_pos``) to warm up, then
         captures the step. Afterwards ``self.token`` holds the newest token and ``self.pos`` its position.
         ``chunk`` > 1 also captures ``chunk`` consecutive steps as one graph (``steps()``): the argmax of step i
         writes its token into ``self.history[i]`` as well, and one launch replaces ``chunk`` (≈9 us of
         graph-launch gap per step on MI355X, profiles/r02b_*). ``temperature`` > 0 replaces the argmax with the
-        fused top-k sampler (ops.sample_topk, ``top_k`` 1..1024, RNG state ``rng``: generate.base.SamplerRNG)."""
+        fused top-k sampler (ops.sample_topk, ``top_k`` 1..1024, RNG state ``rng``: generate.base.SamplerRNG), or,
+        with ``top_p`` < 1, with the nucleus sampler (ops.sample_nucleus, ``top_k`` 1..1024 or None)."""
         dev = first_token.device
         self.model = model
-        self.temperature, self.top_k, self.rng = float(temperature), top_k, rng
-        if self.temperature > 0.0 and (rng is None or top_k is None or not 1 <= top_k <= ops.MAX_TOP_K):
-            raise ValueError("DecodeGraph: sampling needs top_k in [1, 1024] and an rng (generate.base.SamplerRNG)")
+        self.temperature, self.top_k, self.rng, self.top_p = float(temperature), top_k, rng, float(top_p)
+        if self.temperature > 0.0 and (rng is None or not _sampling_ok(self.temperature, top_k, self.top_p)):
+            raise ValueError("DecodeGraph: sampling needs top_k in [1, 1024] and an rng (generate.base.SamplerRNG)"
+                             "; top_k may be None only with 0 < top_p < 1")
         self.token = first_token.reshape(1, 1).to(torch.int32).clone()
         self.pos = torch.tensor([first_pos], dtype=torch.int64, device=dev)
         self.chunk = max(1, int(chunk))
@@ -80,7 +92,11 @@ class DecodeGraph:
         logits = model(self.token, self.pos, last_token_only=True,
                        embedded=self.x_emb if (fuse and embedded) else None).reshape(-1)
         table = model.transformer.wte.weight if fuse else None
-        if self.temperature > 0.0:
+        if self.temperature > 0.0 and self.top_p < 1.0:
+            ops.sample_nucleus(logits, self.top_k, self.top_p, self.temperature, seed=self.rng.seed,
+                               counter=self.rng.counter, out_idx=idx_out, token_out=self.token.view(-1),
+                               pos_inout=self.pos, table=table, emb_out=self.x_emb)
+        elif self.temperature > 0.0:
             ops.sample_topk(logits, self.top_k, self.temperature, seed=self.rng.seed, counter=self.rng.counter,
                             out_idx=idx_out, token_out=self.token.view(-1), pos_inout=self.pos, table=table,
                             emb_out=self.x_emb)
@@ -129,20 +145,21 @@ class WindowDecodeGraph:
     ``pos``, so the host reads ``out`` once per round and nothing per token. ``use_graph=False`` keeps every step
     eager (tests A/B the two). ``temperature`` > 0 ends the step in ``ops.spec_accept_sample`` instead (``top_k``
     1..1024, RNG state ``rng``: generate.base.SamplerRNG, whose counter is the number of tokens sampled so far): row r
-    is sampled with draw number counter + r and a draft is accepted iff it is that sample."""
+    is sampled with draw number counter + r and a draft is accepted iff it is that sample. ``top_p`` < 1 samples the
+    rows with ``ops.spec_accept_sample_nucleus`` (``top_k`` 1..1024 or None)."""
 
     def __init__(self, model, first_token, first_pos: int, *, use_graph: bool = True, temperature: float = 0.0,
-                 top_k: Optional[int] = None, rng=None) -> None:
+                 top_k: Optional[int] = None, rng=None, top_p: float = 1.0) -> None:
         wte = model.transformer.wte.weight
         dev = wte.device
         if not (wte.is_cuda and wte.dtype == torch.bfloat16 and wte.is_contiguous() and wte.shape[1] % 8 == 0):
             raise NotImplementedError("speculative decoding needs a contiguous bf16 embedding table on the GPU with "
                                       "n_embd % 8 == 0")
         model._rows_check("a speculative verify window")  # refuse before any launch
-        self.temperature, self.top_k, self.rng = float(temperature), top_k, rng
-        if self.temperature > 0.0 and (rng is None or top_k is None or not 1 <= top_k <= ops.MAX_TOP_K):
+        self.temperature, self.top_k, self.rng, self.top_p = float(temperature), top_k, rng, float(top_p)
+        if self.temperature > 0.0 and (rng is None or not _sampling_ok(self.temperature, top_k, self.top_p)):
             raise ValueError("WindowDecodeGraph: sampling needs top_k in [1, 1024] and an rng "
-                             "(generate.base.SamplerRNG)")
+                             "(generate.base.SamplerRNG); top_k may be None only with 0 < top_p < 1")
         self.model, self.use_graph = model, use_graph
         self.max_rows = model.MAX_WINDOW
         self.window = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)
@@ -158,7 +175,11 @@ class WindowDecodeGraph:
         model, w = self.model, self.window[:M]
         x = ops.embedding(w, model.transformer.wte.weight, out=self.x_emb[:M])
         logits = model.decode_window(w, self.pos, embedded=x)
-        if self.temperature > 0.0:
+        if self.temperature > 0.0 and self.top_p < 1.0:
+            ops.spec_accept_sample_nucleus(logits, w, self.top_k, self.top_p, self.temperature, seed=self.rng.seed,
+                                           counter=self.rng.counter, out=self.out[:M + 1],
+                                           token_inout=self.window[:1], pos_inout=self.pos, sampled=self.sampled)
+        elif self.temperature > 0.0:
             ops.spec_accept_sample(logits, w, self.top_k, self.temperature, seed=self.rng.seed,
                                    counter=self.rng.counter, out=self.out[:M + 1], token_inout=self.window[:1],
                                    pos_inout=self.pos, sampled=self.sampled)
@@ -200,16 +221,17 @@ class BatchDecodeGraph:
     ``chunk`` steps as one graph whose tokens land in ``history`` (chunk, B)."""
 
     def __init__(self, model, first_tokens: torch.Tensor, first_pos, chunk: int = 1, *, temperature: float = 0.0,
-                 top_k: Optional[int] = None, rngs=None, use_graph: bool = True) -> None:
+                 top_k: Optional[int] = None, rngs=None, use_graph: bool = True, top_p: float = 1.0) -> None:
         """``first_tokens`` (B,): each sequence's newest token; ``first_pos``: its position per sequence. Runs one
         real step eagerly, then captures. ``use_graph=False`` keeps every step eager (tests A/B the two)."""
         dev = first_tokens.device
         B = first_tokens.numel()
         self.model, self.B = model, B
-        self.temperature, self.top_k, self.rngs = float(temperature), top_k, rngs
-        if self.temperature > 0.0 and (rngs is None or len(rngs) != B or top_k is None
-                                       or not 1 <= top_k <= ops.MAX_TOP_K):
-            raise ValueError("BatchDecodeGraph: sampling needs top_k in [1, 1024] and one rng per sequence")
+        self.temperature, self.top_k, self.rngs, self.top_p = float(temperature), top_k, rngs, float(top_p)
+        if self.temperature > 0.0 and (rngs is None or len(rngs) != B
+                                       or not _sampling_ok(self.temperature, top_k, self.top_p)):
+            raise ValueError("BatchDecodeGraph: sampling needs top_k in [1, 1024] and one rng per sequence; top_k "
+                             "may be None only with 0 < top_p < 1")
         wte = model.transformer.wte.weight
         if not (wte.is_cuda and wte.dtype == torch.bfloat16 and wte.is_contiguous() and wte.shape[1] % 8 == 0):
             raise NotImplementedError("batched decode needs a contiguous bf16 embedding table with n_embd % 8 == 0")
@@ -241,7 +263,11 @@ class BatchDecodeGraph:
         table = model.transformer.wte.weight
         for b in range(B):
             out = None if idx_out is None else idx_out[b:b + 1]
-            if self.temperature > 0.0:
+            if self.temperature > 0.0 and self.top_p < 1.0:
+                ops.sample_nucleus(logits[b], self.top_k, self.top_p, self.temperature, seed=self.rngs[b].seed,
+                                   counter=self.rngs[b].counter, out_idx=out, token_out=self.token[b:b + 1],
+                                   pos_inout=self.pos[b:b + 1], table=table, emb_out=self.x_emb[b])
+            elif self.temperature > 0.0:
                 ops.sample_topk(logits[b], self.top_k, self.temperature, seed=self.rngs[b].seed,
                                 counter=self.rngs[b].counter, out_idx=out, token_out=self.token[b:b + 1],
                                 pos_inout=self.pos[b:b + 1], table=table, emb_out=self.x_emb[b])
@@ -276,14 +302,15 @@ class SlotDecodeGraph:
     launch has run eagerly; every launch is on one stream, the graphs are chains without branches."""
 
     def __init__(self, model, B: int, chunk: int = 1, *, temperature: float = 0.0, top_k: Optional[int] = None,
-                 use_graph: bool = True) -> None:
+                 use_graph: bool = True, top_p: float = 1.0) -> None:
         wte = model.transformer.wte.weight
         dev = wte.device
         if not (wte.is_cuda and wte.dtype == torch.bfloat16 and wte.is_contiguous() and wte.shape[1] % 8 == 0):
             raise NotImplementedError("batched decode needs a contiguous bf16 embedding table with n_embd % 8 == 0")
-        self.temperature, self.top_k = float(temperature), top_k
-        if self.temperature > 0.0 and (top_k is None or not 1 <= top_k <= ops.MAX_TOP_K):
-            raise ValueError("SlotDecodeGraph: sampling needs top_k in [1, 1024]")
+        self.temperature, self.top_k, self.top_p = float(temperature), top_k, float(top_p)
+        if self.temperature > 0.0 and not _sampling_ok(self.temperature, top_k, self.top_p):
+            raise ValueError("SlotDecodeGraph: sampling needs top_k in [1, 1024]; top_k may be None only with "
+                             "0 < top_p < 1")
         self.model, self.B, self.use_graph = model, B, use_graph
         self.chunk = max(1, int(chunk))
         self.token = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -314,7 +341,11 @@ class SlotDecodeGraph:
         table = model.transformer.wte.weight
         for b in range(B):
             out = self.history[s, b:b + 1]
-            if self.temperature > 0.0:
+            if self.temperature > 0.0 and self.top_p < 1.0:
+                ops.sample_nucleus(logits[b], self.top_k, self.top_p, self.temperature,
+                                   uniform=self.uniforms[s, b:b + 1], out_idx=out, token_out=self.token[b:b + 1],
+                                   pos_inout=self.pos[b:b + 1], table=table, emb_out=self.x_emb[b])
+            elif self.temperature > 0.0:
                 ops.sample_topk(logits[b], self.top_k, self.temperature, uniform=self.uniforms[s, b:b + 1],
                                 out_idx=out, token_out=self.token[b:b + 1], pos_inout=self.pos[b:b + 1], table=table,
                                 emb_out=self.x_emb[b])
