@@ -127,7 +127,11 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   const int rg = wave * RGW + lane / LPR;
   const int sub = lane % LPR;
   LGA_TRACE(0);
-  // both positions in one scalar round trip (hipcc otherwise waits for input_pos before issuing rope_pos)
+  // The two position loads sit side by side here, but hipcc does not emit them as one round trip: the wave waits for
+  // the kernarg block, then for input_pos, then issues rope_pos behind a second wait, and the q and cos/sin loads
+  // follow. Taking the positions, q and the RoPE tables as leading (preloaded) kernel arguments and loading q beside
+  // the positions leaves one scalar wait ahead of the cos/sin loads; measured, that is 0.1 us of 10.5 per launch, inside
+  // twice the A/B's own spread, so it is not in the product (profiles/attn_launch_head_ab.txt).
   static_assert(!WINDOW || FUSED, "the window form is the fused form per row");
   const long p = WINDOW ? input_pos[0] + t : input_pos[t];
   const long rp_raw = WINDOW ? p : (FUSED ? rope_pos[t] : 0);

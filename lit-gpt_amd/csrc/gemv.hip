@@ -34,8 +34,20 @@ namespace lga {
 #endif
 constexpr int kGemvNW = LGA_GEMV_NW;
 
+// The one-row entry points take their leading arguments as preloadable scalars (gemv_body.h, "Kernel-argument
+// preload"): no kernarg round trip stands between wave start and the first x and weight loads.
 template <int RPR, int CPT, int FMT, bool DUAL, bool NORM, bool RES>
-__global__ void __launch_bounds__(kGemvNW * 64) gemv_q4_kernel(GemvArgs a) {
+__global__ void __launch_bounds__(kGemvNW * 64) gemv_q4_kernel(LGA_GEMV_HEAD_PARAMS, GemvTail r) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  gemv_q4_body<RPR, CPT, FMT, DUAL, NORM, RES, kGemvNW>(gemv_args(x, norm_w, qw, sc, qw2, sc2, N, kg, r), blockIdx.x,
+                                                        smem);
+}
+
+// The whole GemvArgs by value, for the launches off the decode hot path: routed experts (lga_q4_gemv*_experts; grid.y
+// = slots, a.eidx set) and the catch-all geometry of K > 16384 (16 chunks per lane: its nf4 + norm kernels sit at the
+// register limit, and the preloaded form spills a VGPR there).
+template <int RPR, int CPT, int FMT, bool DUAL, bool NORM, bool RES>
+__global__ void __launch_bounds__(kGemvNW * 64) gemv_q4_args_kernel(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   gemv_q4_body<RPR, CPT, FMT, DUAL, NORM, RES, kGemvNW>(a, blockIdx.x, smem);
 }
@@ -52,8 +64,10 @@ __global__ void __launch_bounds__(kGemvNW * 64) gemv_q4_rows_kernel(GemvArgs a, 
 #define LGA_GEMV_K(NORM, RES)                                                                     \
   do {                                                                                            \
     if constexpr (ROWS) gemv_q4_rows_kernel<RPR, CPT, FMT, DUAL, NORM, RES><<<blocks, NT, lds, stream>>>(a, M); \
-    else gemv_q4_kernel<RPR, CPT, FMT, DUAL, NORM, RES><<<blocks, NT, lds, stream>>>(a);          \
+    else if constexpr (CPT > 8) gemv_q4_args_kernel<RPR, CPT, FMT, DUAL, NORM, RES><<<blocks, NT, lds, stream>>>(a); \
+    else gemv_q4_kernel<RPR, CPT, FMT, DUAL, NORM, RES><<<blocks, NT, lds, stream>>>(LGA_GEMV_HEAD_ARGS(a), gemv_tail(a)); \
   } while (0)
+#define LGA_GEMV_E(NORM) gemv_q4_args_kernel<RPR, CPT, FMT, DUAL, NORM, false><<<blocks, NT, lds, stream>>>(a)
 
 template <int RPR, int CPT, int FMT, bool DUAL, bool ROWS = false>
 static void launch(const GemvArgs& a, hipStream_t stream, int M = 1) {
@@ -65,6 +79,13 @@ static void launch(const GemvArgs& a, hipStream_t stream, int M = 1) {
 #endif
   constexpr int NT = kGemvNW * 64;
   const bool norm = a.norm_w != nullptr, res = a.residual != nullptr;
+  if constexpr (!ROWS && CPT <= 8) {
+    if (a.eidx) {  // the routed forms: no residual, and a norm only with the dual (SwiGLU) weights
+      if (DUAL && norm) LGA_GEMV_E(DUAL);
+      else LGA_GEMV_E(false);
+      return;
+    }
+  }
   if (DUAL) {
     if (norm) LGA_GEMV_K(true, false);
     else LGA_GEMV_K(false, false);
@@ -77,11 +98,12 @@ static void launch(const GemvArgs& a, hipStream_t stream, int M = 1) {
   }
 }
 #undef LGA_GEMV_K
+#undef LGA_GEMV_E
 
 template <int RT, int CPT, int FMT, bool DUAL, bool NORM, bool RES>
-__global__ void __launch_bounds__(256) gemv_q4s_kernel(GemvArgs a) {
+__global__ void __launch_bounds__(256) gemv_q4s_kernel(LGA_GEMV_HEAD_PARAMS, GemvTail r) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  gemv_q4_stream<RT, CPT, FMT, DUAL, NORM, RES>(a, smem);
+  gemv_q4_stream<RT, CPT, FMT, DUAL, NORM, RES>(gemv_args(x, norm_w, qw, sc, qw2, sc2, N, kg, r), smem);
 }
 
 template <int RT, int CPT, int FMT, bool DUAL, bool NORM, bool RES>
@@ -92,9 +114,9 @@ __global__ void __launch_bounds__(256) gemv_q4s_rows_kernel(GemvArgs a, int M) {
 
 // greedy decode head: RMSNorm + lm_head GEMV (streaming form) + argmax + next-token embedding in one launch
 template <int RT, int CPT, int FMT, bool NORM>
-__global__ void __launch_bounds__(256) gemv_q4s_amax_kernel(GemvArgs a, AmaxArgs am) {
+__global__ void __launch_bounds__(256) gemv_q4s_amax_kernel(LGA_GEMV_HEAD_PARAMS, GemvTail r, AmaxArgs am) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  gemv_q4_stream<RT, CPT, FMT, false, NORM, false, true>(a, smem, am);
+  gemv_q4_stream<RT, CPT, FMT, false, NORM, false, true>(gemv_args(x, norm_w, qw, sc, qw2, sc2, N, kg, r), smem, am);
 }
 
 static int amax_grid(int N, int K) {  // the streaming form's grid for a plain GEMV (launch_stream, 3 per CU)
@@ -106,7 +128,7 @@ static int amax_grid(int N, int K) {  // the streaming form's grid for a plain G
 #define LGA_GEMV_S(NORM, RES)                                                                      \
   do {                                                                                             \
     if constexpr (ROWS) gemv_q4s_rows_kernel<RT, CPT, FMT, DUAL, NORM, RES><<<blocks, 256, lds, stream>>>(a, M); \
-    else gemv_q4s_kernel<RT, CPT, FMT, DUAL, NORM, RES><<<blocks, 256, lds, stream>>>(a);          \
+    else gemv_q4s_kernel<RT, CPT, FMT, DUAL, NORM, RES><<<blocks, 256, lds, stream>>>(LGA_GEMV_HEAD_ARGS(a), gemv_tail(a)); \
   } while (0)
 
 template <int RT, int CPT, int FMT, bool DUAL, bool ROWS = false>
@@ -360,8 +382,8 @@ extern "C" int lga_q4_gemv_argmax_embed(const void* x, const uint8_t* qweight, c
   const bool norm = norm_weight != nullptr;
 #define LGA_AM(CPT, FMT)                                                                                  \
   do {                                                                                                    \
-    if (norm) lga::gemv_q4s_amax_kernel<2, CPT, FMT, true><<<blocks, 256, lds, stream>>>(a, am);          \
-    else lga::gemv_q4s_amax_kernel<2, CPT, FMT, false><<<blocks, 256, lds, stream>>>(a, am);              \
+    if (norm) lga::gemv_q4s_amax_kernel<2, CPT, FMT, true><<<blocks, 256, lds, stream>>>(LGA_GEMV_HEAD_ARGS(a), lga::gemv_tail(a), am); \
+    else lga::gemv_q4s_amax_kernel<2, CPT, FMT, false><<<blocks, 256, lds, stream>>>(LGA_GEMV_HEAD_ARGS(a), lga::gemv_tail(a), am); \
   } while (0)
   if (cpt == 1) {
     if (kf == 0) LGA_AM(1, 0);

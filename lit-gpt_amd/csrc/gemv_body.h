@@ -48,6 +48,36 @@ struct GemvArgs {
   const uint16_t* probs = nullptr;  // routing probabilities (lga_q4_gemv_experts_pair_combine)
 };
 
+// Kernel-argument preload (gemv.hip's entry points). gfx950 hands a kernel's LEADING scalar arguments to the wave in
+// user SGPRs at launch (-mllvm -amdgpu-kernarg-preload-count, csrc/Makefile): 14 dwords next to the kernarg pointer.
+// A by-value struct is not preloadable, so the entry points take what the first vector loads need as scalars — the
+// activation, the norm weight, the weight and scale pointers of both matrices, N, and K and G packed in one dword
+// (both are multiples of 32 and K <= 32768: K / 32 in the low half, G / 32 in the high half) — and the rest of
+// GemvArgs as a trailing struct, which is fetched from memory while the x and weight loads issue and is first needed
+// by the residual load behind them. Routing (eidx) is never set through these entry points: the routed launches keep
+// the by-value GemvArgs kernel (gemv_q4_args_kernel), so the `if (a.eidx)` of the bodies folds away here.
+struct GemvTail {
+  const uint16_t* bias;
+  const uint16_t* residual;
+  uint16_t* y;
+  float eps;
+  int cb;
+};
+#define LGA_GEMV_HEAD_PARAMS                                                                                     \
+  const uint16_t *x, const uint16_t *norm_w, const uint8_t *qw, const void *sc, const uint8_t *qw2, const void *sc2, \
+      int N, unsigned kg
+#define LGA_GEMV_HEAD_ARGS(a) \
+  (a).x, (a).norm_w, (a).qw, (a).sc, (a).qw2, (a).sc2, (a).N, ((unsigned)(a).K / 32u) | (((unsigned)(a).G / 32u) << 16)
+inline GemvTail gemv_tail(const GemvArgs& a) { return GemvTail{a.bias, a.residual, a.y, a.eps, a.cb}; }
+__device__ __forceinline__ GemvArgs gemv_args(LGA_GEMV_HEAD_PARAMS, const GemvTail& r) {
+  GemvArgs a{x, qw, sc, qw2, sc2, r.bias, r.residual, norm_w, r.y, N, (int)(kg & 0xffffu) * 32, (int)(kg >> 16) * 32, r.eps};
+  a.eidx = nullptr;
+  a.ew = a.es = 0;
+  a.xs = a.n_expert = a.slots = 0;
+  a.cb = r.cb;
+  return a;
+}
+
 // LDS of gemv_q4_body: x pairs (2K B), chunk sums (K/32 floats), norm partials (16), codebook (16), then (LDS_OUT)
 // the workgroup's output rows at a 16-B-aligned offset
 __host__ __device__ inline size_t gemv_out_offset(int K) { return ((size_t)K * 2 + (K / 32) * 4 + 128 + 15) & ~(size_t)15; }
