@@ -510,42 +510,15 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel_kv8(const uint16_t* __res
 }
 
 // The window's KV-append: roped k and v of row r into cache row pos0[0] + r of every group, with the fused kernel's
-// own rope8 on the same operands (the same bits it stores at T = 1). Grid (G, M), one wave: lanes 0..HS/8-1 move k,
-// the next HS/8 move v. A row at or past max_seq stores nothing.
-template <int HS>
-__global__ void __launch_bounds__(64) window_append_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ kc,
-                                                          uint16_t* __restrict__ vc, const int64_t* __restrict__ pos0,
+// own rope8 (and, for fp8 caches, its kv8_quantize8) on the same operands: the same bits, codes and scales it stores
+// at T = 1. Grid (G, M), one wave: lanes 0..HS/8-1 (row group 0) rope k, the next HS/8 (row group 1) carry v. A row
+// at or past max_seq stores nothing. KV8: kc / vc hold e4m3 codes with one scale per row in ksc / vsc (else unused).
+template <bool KV8>
+__global__ void __launch_bounds__(64) window_append_kernel(const uint16_t* __restrict__ qkv, void* __restrict__ kc,
+                                                          void* __restrict__ vc, float* __restrict__ ksc,
+                                                          float* __restrict__ vsc, const int64_t* __restrict__ pos0,
                                                           const float* __restrict__ cos, const float* __restrict__ sin,
                                                           int rope_rows, int n_head, int max_seq) {
-  constexpr int LPR = HS / 8;
-  const int g = blockIdx.x, G = gridDim.x, r = blockIdx.y, qpk = n_head / G;
-  const int lane = threadIdx.x, sub = lane % LPR;
-  const long p = pos0[0] + r;
-  if (lane >= 2 * LPR || p < 0 || p >= max_seq) return;
-  const uint16_t* kvrow = qkv + ((size_t)r * (n_head + 2 * G) + (size_t)g * (qpk + 2) + qpk) * HS + sub * 8;
-  const size_t dst = ((size_t)g * max_seq + p) * HS + sub * 8;
-  if (lane < LPR) {
-    const long rp = min(max(p, 0L), (long)rope_rows - 1);
-    float cs[8], sn[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      cs[i] = cos[(size_t)rp * HS + sub * 8 + i];
-      sn[i] = sin[(size_t)rp * HS + sub * 8 + i];
-    }
-    *(uint4*)(kc + dst) = rope8(*(const uint4*)kvrow, cs, sn, sub);
-  } else {
-    *(uint4*)(vc + dst) = *(const uint4*)(kvrow + HS);
-  }
-}
-
-// window_append_kernel for fp8 caches: row group 0 ropes k, row group 1 holds v, both quantize their row with the
-// fused kernel's kv8_quantize8 on the same operands (the same codes and scales it stores at T = 1).
-__global__ void __launch_bounds__(64) window_append_kv8_kernel(const uint16_t* __restrict__ qkv, uint8_t* __restrict__ kc,
-                                                              uint8_t* __restrict__ vc, float* __restrict__ ksc,
-                                                              float* __restrict__ vsc, const int64_t* __restrict__ pos0,
-                                                              const float* __restrict__ cos,
-                                                              const float* __restrict__ sin, int rope_rows, int n_head,
-                                                              int max_seq) {
   constexpr int HS = 128, LPR = HS / 8;
   const int g = blockIdx.x, G = gridDim.x, r = blockIdx.y, qpk = n_head / G;
   const int lane = threadIdx.x, sub = lane % LPR;
@@ -566,19 +539,22 @@ __global__ void __launch_bounds__(64) window_append_kv8_kernel(const uint16_t* _
   } else {
     x = *(const uint4*)(kvrow + HS);
   }
-  float s;
-  const uint2 c8 = kv8_quantize8(x, s);
   const size_t row = (size_t)g * max_seq + p;
-  *(uint2*)((is_k ? kc : vc) + row * HS + sub * 8) = c8;
-  if (sub == 0) (is_k ? ksc : vsc)[row] = s;
+  if constexpr (KV8) {
+    float s;
+    const uint2 c8 = kv8_quantize8(x, s);
+    *(uint2*)((uint8_t*)(is_k ? kc : vc) + row * HS + sub * 8) = c8;
+    if (sub == 0) (is_k ? ksc : vsc)[row] = s;
+  } else {
+    *(uint4*)((uint16_t*)(is_k ? kc : vc) + row * HS + sub * 8) = x;
+  }
 }
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 // ---------------------------------------------------------------------------------------------------------------
-// Prefill (T >= 16): flash attention on MFMA, swapped form. A workgroup = 4 waves x 32 query rows of one head;
-// key tiles of 64 rows stream through a double-buffered LDS image (register-staged: the next tile's global loads are issued
-// before this tile's MFMAs and written after them). Per 32-key half-tile, S^T = K . Q^T on v_mfma_f32_32x32x16_bf16
+// Prefill (T >= 16): flash attention on MFMA, swapped form (attn_prefill_pair_kernel). A wave owns 32 query rows of
+// one head; key tiles of 64 rows stream through LDS. Per 32-key half-tile, S^T = K . Q^T on v_mfma_f32_32x32x16_bf16
 // (A = K rows from LDS, B = this wave's Q^T held in registers), so lane l holds the scores of ONE query (l % 32)
 // for 16 keys and its partner lane l ^ 32 the other 16: the online-softmax max / sum are in-lane chains plus one
 // exchange. P goes to bf16 in registers and two v_permlane32_swap per 16 keys regroup it into the B operand of
@@ -587,15 +563,13 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 // exp(m_old - m_new) is a per-lane scalar, skipped when no row max of the wave moved. Causal masking only on the
 // tiles that cross a row's position (a 32-bit compare + select per element, on those tiles only); the scores stay
 // raw — the max runs on them and one fma(s, scale log2 e, -m) per element feeds v_exp_f32 (max(s) c == max(s c) for
-// c > 0). K / V tiles are staged by buffer loads (the whole row offset in the per-thread voffset; rows past the
-// cache read as zeros by the range check) and every LDS address is a per-lane base plus a compile-time offset (the
-// tile loop is unrolled by the two buffers). Grid: 1-D, `order` 1 pairs the two workgroups a CU holds — the first
-// half walks query blocks nblk-1 .. nblk/2, the second half blocks 0 .. nblk/2-1, so workgroups i and i + half sum
-// to a constant number of key tiles and share a head (its K / V in one XCD's L2).
-// Llama-2-7B, T = 2048: 64-65 us per layer = 529-540 TFLOP/s causal, 652-667 TFLOP/s with every row seeing all
-// keys (tools/prefill_attn_bench.py; round 2's kernel: 88-90 us). PMC (profiles/r03c_prefill_fa_pmc.txt): MFMA busy
-// 0.24, SQ_WAIT_ANY 30 % / SQ_WAIT_INST_ANY 35 % of wave cycles, L2 hit 85 % — latency inside each wave (K read ->
-// S MFMA -> max -> exp -> P -> PV chains), not bandwidth; one workgroup per CU is only 19 % slower.
+// c > 0). Every LDS address is a per-lane base plus a compile-time offset.
+// This per-wave arithmetic is round 3's (a 4-wave workgroup per 128-row query block, K / V register-staged through a
+// double-buffered LDS image; no longer in the tree): Llama-2-7B, T = 2048, 64-65 us per layer =
+// 529-540 TFLOP/s causal, 652-667 TFLOP/s with every row seeing all keys (tools/prefill_attn_bench.py; round 2's
+// kernel: 88-90 us). Its PMC (profiles/r03c_prefill_fa_pmc.txt): MFMA busy 0.24, SQ_WAIT_ANY 30 % / SQ_WAIT_INST_ANY
+// 35 % of wave cycles, L2 hit 85 % — latency inside each wave (K read -> S MFMA -> max -> exp -> P -> PV chains), not
+// bandwidth; one workgroup per CU was only 19 % slower.
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef short i16x4_t __attribute__((ext_vector_type(4)));
 typedef short i16x8_t __attribute__((ext_vector_type(8)));
@@ -610,231 +584,17 @@ __device__ __forceinline__ int kv_off(int row, int ch) {
   return row * (HS * 2) + 16 * (ch ^ sw);
 }
 
-template <int HS>
-__global__ void __launch_bounds__(256, 2) attn_prefill_kernel(const uint16_t* __restrict__ q,
-                                                                const uint16_t* __restrict__ kc,
-                                                                const uint16_t* __restrict__ vc,
-                                                                const int64_t* __restrict__ input_pos,
-                                                                uint16_t* __restrict__ y, int T, int n_head, int G,
-                                                                int max_seq, float scale, int order) {
-  constexpr int KT = 64;              // keys per tile
-  constexpr int CH = HS / 8;          // 16-B chunks per key row
-  constexpr int DK = HS / 16;         // 32x32x16 k-steps over the head dim (S^T)
-  constexpr int DT = HS / 32;         // 32-row tiles of O^T
-  constexpr int TB = KT * HS * 2;     // bytes of one K or V tile image
-  constexpr int LPT = KT * CH / 256;  // 16-B chunks per thread per tile (K and V each)
-  constexpr int RPI = 256 / CH;       // key rows between a thread's consecutive chunks
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][TB];  // [buffer][K | V]
-  __shared__ int s_pos[2][4];                                           // per wave: max / min row position
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hh = lane >> 5, lq = lane & 31;
-  const int nblk = (T + 127) / 128;
-  // order 0: longest first; order 1: the first half of the grid walks blocks nblk-1 .. nblk/2, the second half
-  // blocks 0 .. nblk/2-1, so workgroups i and i + half hold key-tile counts summing to a constant and the same head
-  // (its K / V stays in one XCD's L2 when half is a multiple of 8)
-  const int nhi = (nblk - nblk / 2) * n_head;
-  const int i = blockIdx.x;
-  const bool lo_half = order == 1 && i >= nhi;
-  const int jj = lo_half ? i - nhi : i;
-  const int head = jj % n_head, g = head / (n_head / G);
-  const int blk = lo_half ? jj / n_head : nblk - 1 - jj / n_head;
-  const int q0 = blk * 128 + wave * 32;
-  const int t = q0 + lq;
-  const int mypos = t < T ? (int)input_pos[t] : -1;
-  {
-    int mx = mypos, mn = t < T ? mypos : INT_MAX;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      mx = max(mx, __shfl_xor(mx, o));
-      mn = min(mn, __shfl_xor(mn, o));
-    }
-    if (lane == 0) {
-      s_pos[0][wave] = mx;
-      s_pos[1][wave] = mn;
-    }
-  }
-  bf16x8_t qb[DK];  // Q^T fragments (B operand): lane l holds Q[t][ks*16 + 8*hh .. +8]
-  {
-    const uint16_t* qr = q + ((size_t)min(t, T - 1) * n_head + head) * HS + 8 * hh;
-#pragma unroll
-    for (int ks = 0; ks < DK; ++ks) qb[ks] = *(const bf16x8_t*)(qr + ks * 16);
-  }
-  __syncthreads();
-  const int wmax = s_pos[0][wave], wmin = s_pos[1][wave];
-  const int bmax = min(max(max(s_pos[0][0], s_pos[0][1]), max(s_pos[0][2], s_pos[0][3])), max_seq - 1);
-  const int ntiles = (bmax + 1 + KT - 1) / KT;
-
-  // K / V staging: thread tid moves chunk tid % CH of rows tid / CH + RPI i of every tile
-  const __amdgpu_buffer_rsrc_t krs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(kc + (size_t)g * max_seq * HS), (short)0, max_seq * HS * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t vrs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(vc + (size_t)g * max_seq * HS), (short)0, max_seq * HS * 2, 0x00020000);
-  const int gvoff = ((tid / CH) * HS + (tid % CH) * 8) * 2;
-  u32x4_t kr[LPT], vr[LPT];  // tile t + 1 in flight under tile t
-  int soff[LPT];
-#pragma unroll
-  for (int i = 0; i < LPT; ++i) soff[i] = kv_off<HS>(tid / CH + RPI * i, tid % CH);
-  // the whole byte offset rides in voffset: the buffer range check covers voffset only (soffset is added after
-  // it), so rows past max_seq — the last partial tile and the one-tile-ahead prefetch — read as zeros instead of
-  // past the group's cache
-#ifndef LGA_FA_EXP
-#define LGA_FA_EXP 0  // lab only (tools/prefill_attn_bench.py): 1 no tile math, 2 no global loads, 3 neither
-#endif
-  auto gload = [&](int k0) {
-    if (LGA_FA_EXP & 2) return;
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) {
-      const int off = gvoff + (k0 + RPI * i) * HS * 2;
-      kr[i] = __builtin_amdgcn_raw_buffer_load_b128(krs, off, 0, 0);
-      vr[i] = __builtin_amdgcn_raw_buffer_load_b128(vrs, off, 0, 0);
-    }
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) {
-      *(u32x4_t*)(lds[buf][0] + soff[i]) = kr[i];
-      *(u32x4_t*)(lds[buf][1] + soff[i]) = vr[i];
-    }
-  };
-  // LDS read bases: K row lq (+ 32 st), chunk 2 ks + hh; V^T transposed reads (16-lane group grp, quad qq, pair pp)
-  int koff[DK];
-#pragma unroll
-  for (int ks = 0; ks < DK; ++ks) koff[ks] = kv_off<HS>(lq, 2 * ks + hh);
-  const int gi = lane & 15, qq = gi >> 2, pp = gi & 3, grp = lane >> 4;
-  int voff0[DT], voff1[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) {
-    const int ch = ((dt * 32 + 16 * (grp & 1)) >> 3) + (pp >> 1);
-    voff0[dt] = kv_off<HS>(8 * (grp >> 1) + qq, ch) + 8 * (pp & 1);
-    voff1[dt] = kv_off<HS>(8 * (grp >> 1) + 4 + qq, ch) + 8 * (pp & 1);
-  }
-
-  f32x16_t o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[dt][r] = 0.0f;
-  float m = -INFINITY, l = 0.0f;  // m in the scaled log2 domain; l = this lane's 16-key half of the row sum
-  const float sl2 = scale * 1.4426950408889634f;
-
-  auto tile = [&](const unsigned char* K, const unsigned char* V, int k0) {
-    if (LGA_FA_EXP & 1) return;
-    // S^T of the two 32-key halves as two interleaved accumulation chains
-    f32x16_t sacc[2];
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[st][r] = 0.0f;
-#pragma unroll
-    for (int ks = 0; ks < DK; ++ks)
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const bf16x8_t ka = *(const bf16x8_t*)(K + st * 32 * HS * 2 + koff[ks]);
-        sacc[st] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qb[ks], sacc[st], 0, 0, 0);
-      }
-    if (__builtin_amdgcn_readfirstlane(k0 + KT - 1 > wmin)) {  // a row of this wave ends inside the tile
-#pragma unroll
-      for (int st = 0; st < 2; ++st)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (k0 + st * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh > mypos) sacc[st][r] = -INFINITY;
-    }
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int st = 0; st < 2; ++st)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, sacc[st][r]);
-    {
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(tmax), __float_as_uint(tmax), false, false);
-      tmax = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));  // both halves of the row
-    }
-    const float mnew = fmaxf(m, tmax * sl2);
-    const float mref = mnew == -INFINITY ? 0.0f : mnew;  // rows with no visible key yet: p = 0, o stays 0
-    if (!__all(mnew == m)) {                              // some row max moved: rescale (exactly; no threshold)
-      const float c = __builtin_amdgcn_exp2f(m - mref);
-      l *= c;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] *= c;
-    }
-    m = mnew;
-    // P^T . V per 16-key k-step kk: its 8 exponentials (half-tile kk / 2, registers 8 (kk & 1) .. +7) become the
-    // B operand just before its DT MFMAs, so the next k-step's exponentials can issue under them
-    float rs = 0.0f;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const int st = kk >> 1, r0 = 8 * (kk & 1);
-      float x[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        x[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[st][r0 + e], sl2, -mref));
-        rs += x[e];
-      }
-      const uint32_t w0 = pack2(x[0], x[1]), w1 = pack2(x[2], x[3]);
-      const uint32_t w2 = pack2(x[4], x[5]), w3 = pack2(x[6], x[7]);
-      const auto a = __builtin_amdgcn_permlane32_swap(w0, w2, false, false);
-      const auto b = __builtin_amdgcn_permlane32_swap(w1, w3, false, false);
-      const u32x4_t f = {a[0], b[0], a[1], b[1]};
-      const bf16x8_t pb = __builtin_bit_cast(bf16x8_t, f);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        typedef __attribute__((address_space(3))) i16x4_t lds_i16x4;
-        const i16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)(V + kk * 16 * HS * 2 + voff0[dt]));
-        const i16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_i16x4*)(V + kk * 16 * HS * 2 + voff1[dt]));
-        const i16x8_t vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, vf), pb, o[dt], 0, 0, 0);
-      }
-    }
-    l += rs;
-  };
-
-  // unrolled by the two buffers so every LDS address is base + constant; tile t + 1's loads are in flight under
-  // tile t's MFMAs (past the cache: zeros, unused) and written to the other buffer after them (a second register
-  // set, two tiles ahead, measured no faster: the loop is latency-bound inside the wave, not on the loads)
-  if (ntiles > 0) {
-    gload(0);
-    lstore(0);
-  }
-  __syncthreads();
-  for (int it = 0; it < ntiles; it += 2) {
-    const int k0 = it * KT;
-    gload(k0 + KT);
-    if (k0 <= wmax) tile(lds[0][0], lds[0][1], k0);
-    lstore(1);
-    __syncthreads();
-    if (it + 1 >= ntiles) break;
-    gload(k0 + 2 * KT);
-    if (k0 + KT <= wmax) tile(lds[1][0], lds[1][1], k0 + KT);
-    lstore(0);
-    __syncthreads();
-  }
-  l += __shfl_xor(l, 32);
-  // y[t][head * HS + d] = O^T[d][t] / l, d = dt * 32 + crow(r): pairs (r, r + 1) are adjacent columns
-  if (t < T) {
-    const float inv = 1.0f / l;
-    uint16_t* yr = y + ((size_t)t * n_head + head) * HS;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        *(uint32_t*)(yr + d) = pack2(o[dt][r] * inv, o[dt][r + 1] * inv);
-      }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Prefill, paired form (default): one 512-thread workgroup per (head, block pair) holds query blocks hi = nblk-1-p
+// The paired form: one 512-thread workgroup per (head, block pair) holds query blocks hi = nblk-1-p
 // (waves 0-3) and lo = p (waves 4-7) of 128 rows and streams the head's K / V ONCE for both — key tile t serves
 // every wave whose rows reach it (26 % fewer L2 -> LDS bytes than a workgroup per block at T = 2048, and every SIMD
 // holds one hi and one lo wave: 2 (nblk + 1) key tiles per SIMD whatever p). K / V tiles reach LDS by LDS-DMA
 // (`buffer_load_dwordx4 ... lds`, range-checked: rows past the cache land as zeros) into a 4-stage ring, three tiles
 // ahead of the math, with no staging registers; a raw s_barrier per tile after a counted vmcnt. The LDS reads are
 // inline asm with counted lgkmcnt waits (hipcc would wait for every DMA in flight before a compiler-visible LDS
-// read, not telling the stages apart). Per wave the arithmetic is attn_prefill_kernel's, op for op.
-// an LDS read at a compile-time offset (after unrolling) in inline asm; the host pass, which only type-checks the
-// kernel body, cannot take the "i" operand of a non-constant expression
+// read, not telling the stages apart).
+//
+// LGA_DS_READ: an LDS read at a compile-time offset (after unrolling) in inline asm; the host pass, which only
+// type-checks the kernel body, cannot take the "i" operand of a non-constant expression
 #ifdef __HIP_DEVICE_COMPILE__
 #define LGA_DS_READ(op, dst, addr, off) \
   asm volatile(op " %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off) : "memory")
@@ -1125,26 +885,62 @@ __global__ void __launch_bounds__(512, 1) attn_prefill_pair_kernel(const uint16_
 #define LGA_ATTN_Q8 2, 4
 #endif
 
-// the slot strides and the idle flags of a BATCH launch (zeros / null for every other form)
-struct BatchArgs {
-  long slot_stride = 0, scale_slot_stride = 0;
-  const int* active = nullptr;
+// One attention call as the entry points describe it. kRows: lga_attention (q (T, H, hs) already roped, no append);
+// the other three are the fused decode forms on the qkv projection rows (the FUSED / WINDOW / BATCH comments above).
+enum AttnForm { kRows, kOne, kWindow, kBatch };
+struct AttnCall {
+  const char* name;  // the entry point, for its messages
+  AttnForm form;
+  bool kv8;  // fp8 caches: kc / vc hold codes, ksc / vsc the row scales
+  int rows;  // T, 1, M or B
+  const void* q;  // q, or the qkv rows of a fused form
+  void *kc, *vc;
+  float *ksc, *vsc;
+  const int64_t *pos, *rope_pos;
+  const float *cos, *sin;
+  int rope_rows;
+  void* y;
+  float* ws;
+  unsigned* cnt;
+  long long slot_stride, scale_slot_stride;  // kBatch: elements between two sequences' caches / scale rows
+  const int32_t* active;                     // kBatch: idle flags, may be null
+  int H, G, hs, rope_n_elem, max_seq, n_splits;
+  float scale;
+  hipStream_t stream;
 };
 
-template <int HS, int QPK, int UNR, int NW, bool FUSED, bool WINDOW = false, bool KV8 = false, bool BATCH = false>
-static void launch_one(dim3 grid, hipStream_t stream, const void* q, void* kc, void* vc, const int64_t* pos, void* y,
-                       float* ws, unsigned* cnt, int H, int max_seq, float scale, const int64_t* rope_pos,
-                       const float* cos, const float* sin, int rope_rows, int hsplit, float* ksc, float* vsc,
-                       const BatchArgs& ba) {
-  if constexpr (KV8) {
-    attn_kernel_kv8<HS, QPK, UNR, NW, BATCH, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
-        (const uint16_t*)q, (uint8_t*)kc, (uint8_t*)vc, ksc, vsc, pos, (uint16_t*)y, ws, cnt, H, max_seq, scale,
-        rope_pos, cos, sin, rope_rows, hsplit, ba.slot_stride, ba.scale_slot_stride, ba.active);
-  } else {
-    attn_kernel<HS, QPK, UNR, NW, BATCH, FUSED, LGA_ATTN_PIPE != 0, WINDOW><<<grid, NW * 64, 0, stream>>>(
-        (const uint16_t*)q, (uint16_t*)kc, (uint16_t*)vc, pos, (uint16_t*)y, ws, cnt, H, max_seq, scale, rope_pos, cos,
-        sin, rope_rows, hsplit, ba.slot_stride, ba.active);
+// the kernel instantiation of a call, one (heads per workgroup, keys in flight, waves) configuration: hs 64 exists
+// for kRows only, the fp8 kernels for the fused forms only (attn_body's static_asserts)
+template <int HS, int QPK, int UNR, int NW>
+static void attn_launch_cfg(const AttnCall& c, dim3 grid, int hsplit) {
+  constexpr bool PIPE = LGA_ATTN_PIPE != 0;
+#define LGA_BF16(BATCH, FUSED, WINDOW)                                                                             \
+  attn_kernel<HS, QPK, UNR, NW, BATCH, FUSED, PIPE, WINDOW><<<grid, NW * 64, 0, c.stream>>>(                       \
+      (const uint16_t*)c.q, (uint16_t*)c.kc, (uint16_t*)c.vc, c.pos, (uint16_t*)c.y, c.ws, c.cnt, c.H, c.max_seq,  \
+      c.scale, c.rope_pos, c.cos, c.sin, c.rope_rows, hsplit, (long)c.slot_stride, c.active)
+#define LGA_FP8(BATCH, WINDOW)                                                                                     \
+  attn_kernel_kv8<HS, QPK, UNR, NW, BATCH, PIPE, WINDOW><<<grid, NW * 64, 0, c.stream>>>(                          \
+      (const uint16_t*)c.q, (uint8_t*)c.kc, (uint8_t*)c.vc, c.ksc, c.vsc, c.pos, (uint16_t*)c.y, c.ws, c.cnt, c.H, \
+      c.max_seq, c.scale, c.rope_pos, c.cos, c.sin, c.rope_rows, hsplit, (long)c.slot_stride,                      \
+      (long)c.scale_slot_stride, c.active)
+#define LGA_FUSED(BATCH, WINDOW)                    \
+  do {                                              \
+    if (c.kv8) LGA_FP8(BATCH, WINDOW);              \
+    else LGA_BF16(BATCH, true, WINDOW);             \
+    return;                                         \
+  } while (0)
+  if constexpr (HS == 128) {
+    switch (c.form) {
+      case kOne: LGA_FUSED(false, false);
+      case kWindow: LGA_FUSED(false, true);
+      case kBatch: LGA_FUSED(true, false);
+      case kRows: break;
+    }
   }
+  LGA_BF16(false, false, false);
+#undef LGA_FUSED
+#undef LGA_BF16
+#undef LGA_FP8
 }
 
 // head slices per query group: split a group's heads over more workgroups while the launch would fill at most half
@@ -1162,88 +958,96 @@ static int attn_hsplit(int T, int G, int qpk, int n_splits) {
   return h;
 }
 
-template <int HS, bool FUSED, bool WINDOW = false, bool KV8 = false, bool BATCH = false>
-static int launch_hs(const void* q, void* kc, void* vc, const int64_t* pos, void* y, float* ws, unsigned* cnt, int T,
-                     int H, int G, int max_seq, int n_splits, float scale, const int64_t* rope_pos, const float* cos,
-                     const float* sin, int rope_rows, hipStream_t stream, float* ksc = nullptr, float* vsc = nullptr,
-                     const BatchArgs& ba = BatchArgs()) {
+// Every entry point below: the argument checks (nothing is dereferenced or launched before they pass), the window's
+// append, the grid, the kernel.
+static int attn_launch(const AttnCall& c) {
+  const bool fused = c.form != kRows;
+  const bool many = c.form == kWindow || c.form == kBatch;
+  const int qpk = c.G > 0 ? c.H / c.G : 0;
+  const long long seq_rows = (long long)c.G * c.max_seq;
+  const bool ptrs = c.q && c.kc && c.vc && c.pos && c.y && (!fused || (c.rope_pos && c.cos && c.sin)) &&
+                    (!c.kv8 || (c.ksc && c.vsc));
+  const char* bad =
+      !ptrs ? "null pointer"
+      : many && !(c.rows >= 1 && c.rows <= 8) ? (c.form == kWindow ? "M must be in [1, 8]" : "B must be in [1, 8]")
+      : !(c.rows > 0 && c.G > 0 && c.H % c.G == 0) ? "bad head geometry"
+      : fused && !(c.hs == 128 && c.rope_n_elem == 128)
+          ? "needs head_size == rope_n_elem == 128 (else: rope_kv_append + attention)"
+      : !fused && c.hs != 128 && c.hs != 64 ? "head_size must be 64 or 128"
+      : fused && qpk != 1 && qpk != 2 && qpk != 4 && qpk != 8 ? "q_per_kv must be 1, 2, 4 or 8"
+      : fused && !(c.rope_rows > 0 && c.max_seq > 0) ? "empty rope cache or kv cache"
+      : !(c.n_splits >= 1 && c.n_splits <= 256) ? "n_splits must be in [1, 256]"
+      : !(c.n_splits == 1 || (c.ws && c.cnt)) ? "split attention needs workspace + counters"
+      : c.form == kBatch && c.slot_stride < seq_rows * c.hs
+          ? "slot_stride below one sequence's G * max_seq * head_size elements"
+      : c.form == kBatch && c.kv8 && c.scale_slot_stride < seq_rows
+          ? "scale_slot_stride below one sequence's G * max_seq scales"
+          : nullptr;
+  if (bad) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: %s", c.name, bad);
+    lga_set_error(msg);
+    return (int)hipErrorInvalidValue;
+  }
+  if (!fused && c.rows >= 16 && c.n_splits == 1) {  // prefill: flash attention on MFMA, any heads per group
+    const dim3 grid((((c.rows + 127) / 128 + 1) / 2) * c.H);
+#define LGA_PREFILL(HS)                                                                                          \
+  attn_prefill_pair_kernel<HS><<<grid, 512, 0, c.stream>>>((const uint16_t*)c.q, (const uint16_t*)c.kc,          \
+                                                           (const uint16_t*)c.vc, c.pos, (uint16_t*)c.y, c.rows, \
+                                                           c.H, c.G, c.max_seq, c.scale)
+    if (c.hs == 128) LGA_PREFILL(128);
+    else LGA_PREFILL(64);
+#undef LGA_PREFILL
+    LGA_LAUNCH_RETURN();
+  }
+  if (c.form == kWindow) {  // two launches on the stream: the append of all M rows, then the M-row attention
+    const dim3 grid(c.G, c.rows);
+    if (c.kv8)
+      window_append_kernel<true><<<grid, 64, 0, c.stream>>>((const uint16_t*)c.q, c.kc, c.vc, c.ksc, c.vsc, c.pos,
+                                                            c.cos, c.sin, c.rope_rows, c.H, c.max_seq);
+    else
+      window_append_kernel<false><<<grid, 64, 0, c.stream>>>((const uint16_t*)c.q, c.kc, c.vc, nullptr, nullptr, c.pos,
+                                                             c.cos, c.sin, c.rope_rows, c.H, c.max_seq);
+  }
   // a window row, a batch row: the slices of its T = 1 launch
-  const int hsplit = attn_hsplit(WINDOW || BATCH ? 1 : T, G, H / G, n_splits);
-  const dim3 grid(n_splits, G * hsplit, T);
-#define LGA_ATTN(QPK, CFG)                                                                                        \
-  launch_one<HS, QPK, CFG, FUSED, WINDOW, KV8, BATCH>(grid, stream, q, kc, vc, pos, y, ws, cnt, H, max_seq, scale,     \
-                                                      rope_pos, cos, sin, rope_rows, hsplit, ksc, vsc, ba)
-  switch (H / G / hsplit) {
+  const int hsplit = attn_hsplit(many ? 1 : c.rows, c.G, qpk, c.n_splits);
+  const dim3 grid(c.n_splits, c.G * hsplit, c.rows);
+#define LGA_ATTN(QPK, CFG)                                                  \
+  do {                                                                      \
+    if (c.hs == 128) attn_launch_cfg<128, QPK, CFG>(c, grid, hsplit);       \
+    else attn_launch_cfg<64, QPK, CFG>(c, grid, hsplit);                    \
+  } while (0)
+  switch (qpk / hsplit) {
     case 1:  // one head per group: 8 waves x 2 keys in flight when the groups are few (TP ranks: G = 4 7.9 vs 8.2 us,
              // G = 8 8.0 vs 8.7 at 16 splits; profiles/r04u_attn_head_slices.txt), else 4 x 4 (Llama-2-7B, G = 32)
-      if (G * hsplit <= 16) LGA_ATTN(1, LGA_ATTN_Q1_FEW);
+      if (c.G * hsplit <= 16) LGA_ATTN(1, LGA_ATTN_Q1_FEW);
       else LGA_ATTN(1, LGA_ATTN_Q1);
       break;
     case 2: LGA_ATTN(2, LGA_ATTN_Q2); break;
     case 4: LGA_ATTN(4, LGA_ATTN_Q4); break;
     case 8: LGA_ATTN(8, LGA_ATTN_Q8); break;
+    // (kRows below 16 rows only: the prefill kernel takes any q_per_kv, and the fused forms were checked above)
     default: lga_set_error("lga_attention: q_per_kv must be 1, 2, 4 or 8"); return (int)hipErrorInvalidValue;
   }
 #undef LGA_ATTN
-  return 0;
+  LGA_LAUNCH_RETURN();
 }
 
 }  // namespace lga
 
 int lga::preload_attention() {
-  return lga::preload(lga::attn_prefill_kernel<128>) + lga::preload(lga::attn_prefill_kernel<64>) +
-         lga::preload(lga::attn_prefill_pair_kernel<128>) + lga::preload(lga::attn_prefill_pair_kernel<64>);
+  return lga::preload(lga::attn_prefill_pair_kernel<128>) + lga::preload(lga::attn_prefill_pair_kernel<64>);
 }
+
+// The entry points (include/litgpt_amd.h states each form's contract): fill the call, launch it.
+using lga::AttnCall;
 
 extern "C" int lga_attention(const void* q, const void* k_cache, const void* v_cache, const int64_t* input_pos,
                              void* y, float* workspace, unsigned* counters, int T, int n_head, int n_query_groups,
                              int head_size, int max_seq, int n_splits, float scale, hipStream_t stream) {
-  LGA_CHECK_ARG(q && k_cache && v_cache && input_pos && y, "lga_attention: null pointer");
-  LGA_CHECK_ARG(T > 0 && n_query_groups > 0 && n_head % n_query_groups == 0, "lga_attention: bad head geometry");
-  LGA_CHECK_ARG(n_splits >= 1 && n_splits <= 256, "lga_attention: n_splits must be in [1, 256]");
-  LGA_CHECK_ARG(n_splits == 1 || (workspace && counters), "lga_attention: split attention needs workspace + counters");
-  if (T >= 16 && n_splits == 1 && (head_size == 128 || head_size == 64)) {  // prefill: flash attention on MFMA
-#ifndef LGA_FA_PAIR
-#define LGA_FA_PAIR 1
-#endif
-    if (LGA_FA_PAIR) {
-      const dim3 grid((((T + 127) / 128 + 1) / 2) * n_head);
-      if (head_size == 128)
-        lga::attn_prefill_pair_kernel<128><<<grid, 512, 0, stream>>>((const uint16_t*)q, (const uint16_t*)k_cache,
-                                                                     (const uint16_t*)v_cache, input_pos, (uint16_t*)y,
-                                                                     T, n_head, n_query_groups, max_seq, scale);
-      else
-        lga::attn_prefill_pair_kernel<64><<<grid, 512, 0, stream>>>((const uint16_t*)q, (const uint16_t*)k_cache,
-                                                                    (const uint16_t*)v_cache, input_pos, (uint16_t*)y,
-                                                                    T, n_head, n_query_groups, max_seq, scale);
-      LGA_LAUNCH_RETURN();
-    }
-    const dim3 grid(((T + 127) / 128) * n_head);
-    if (head_size == 128)
-      lga::attn_prefill_kernel<128><<<grid, 256, 0, stream>>>((const uint16_t*)q, (const uint16_t*)k_cache,
-                                                              (const uint16_t*)v_cache, input_pos, (uint16_t*)y, T,
-                                                              n_head, n_query_groups, max_seq, scale, 1);
-    else
-      lga::attn_prefill_kernel<64><<<grid, 256, 0, stream>>>((const uint16_t*)q, (const uint16_t*)k_cache,
-                                                             (const uint16_t*)v_cache, input_pos, (uint16_t*)y, T,
-                                                             n_head, n_query_groups, max_seq, scale, 1);
-    LGA_LAUNCH_RETURN();
-  }
-  int rc;
-  if (head_size == 128)
-    rc = lga::launch_hs<128, false>((const void*)q, (void*)k_cache, (void*)v_cache, input_pos, y, workspace, counters,
-                                    T, n_head, n_query_groups, max_seq, n_splits, scale, nullptr, nullptr, nullptr, 0,
-                                    stream);
-  else if (head_size == 64)
-    rc = lga::launch_hs<64, false>((const void*)q, (void*)k_cache, (void*)v_cache, input_pos, y, workspace, counters,
-                                   T, n_head, n_query_groups, max_seq, n_splits, scale, nullptr, nullptr, nullptr, 0,
-                                   stream);
-  else {
-    lga_set_error("lga_attention: head_size must be 64 or 128");
-    return (int)hipErrorInvalidValue;
-  }
-  if (rc) return rc;
-  LGA_LAUNCH_RETURN();
+  return lga::attn_launch(AttnCall{"lga_attention", lga::kRows, false, T, q, (void*)k_cache, (void*)v_cache, nullptr,
+                                   nullptr, input_pos, nullptr, nullptr, nullptr, 0, y, workspace, counters, 0, 0,
+                                   nullptr, n_head, n_query_groups, head_size, 0, max_seq, n_splits, scale, stream});
 }
 
 // Decode step (T = 1) with RoPE + KV-append fused in: qkv is the fused projection row ([G][q_per_kv + 2][hs]
@@ -1255,20 +1059,10 @@ extern "C" int lga_attention_decode_fused(const void* qkv, void* k_cache, void* 
                                           void* y, float* workspace, unsigned* counters, int n_head,
                                           int n_query_groups, int head_size, int rope_n_elem, int max_seq,
                                           int n_splits, float scale, hipStream_t stream) {
-  LGA_CHECK_ARG(qkv && k_cache && v_cache && cache_pos && rope_pos && cos && sin && y,
-                "lga_attention_decode_fused: null pointer");
-  LGA_CHECK_ARG(n_query_groups > 0 && n_head % n_query_groups == 0, "lga_attention_decode_fused: bad head geometry");
-  LGA_CHECK_ARG(head_size == 128 && rope_n_elem == 128,
-                "lga_attention_decode_fused: needs head_size == rope_n_elem == 128 (use rope_kv_append + attention)");
-  LGA_CHECK_ARG(rope_rows > 0 && max_seq > 0, "lga_attention_decode_fused: empty rope cache or kv cache");
-  LGA_CHECK_ARG(n_splits >= 1 && n_splits <= 256, "lga_attention_decode_fused: n_splits must be in [1, 256]");
-  LGA_CHECK_ARG(n_splits == 1 || (workspace && counters),
-                "lga_attention_decode_fused: split attention needs workspace + counters");
-  const int rc = lga::launch_hs<128, true>(qkv, k_cache, v_cache, cache_pos, y, workspace, counters, 1, n_head,
-                                           n_query_groups, max_seq, n_splits, scale, rope_pos, cos, sin, rope_rows,
-                                           stream);
-  if (rc) return rc;
-  LGA_LAUNCH_RETURN();
+  return lga::attn_launch(AttnCall{"lga_attention_decode_fused", lga::kOne, false, 1, qkv, k_cache, v_cache, nullptr,
+                                   nullptr, cache_pos, rope_pos, cos, sin, rope_rows, y, workspace, counters, 0, 0,
+                                   nullptr, n_head, n_query_groups, head_size, rope_n_elem, max_seq, n_splits, scale,
+                                   stream});
 }
 
 // Speculative verify window: M rows of ONE sequence at consecutive positions pos0[0] + r (cache and rope position, read
@@ -1279,56 +1073,24 @@ extern "C" int lga_attention_decode_window(const void* qkv, void* k_cache, void*
                                            float* workspace, unsigned* counters, int M, int n_head,
                                            int n_query_groups, int head_size, int rope_n_elem, int max_seq,
                                            int n_splits, float scale, hipStream_t stream) {
-  LGA_CHECK_ARG(qkv && k_cache && v_cache && pos0 && cos && sin && y, "lga_attention_decode_window: null pointer");
-  LGA_CHECK_ARG(M >= 1 && M <= 8, "lga_attention_decode_window: M must be in [1, 8]");
-  LGA_CHECK_ARG(n_query_groups > 0 && n_head % n_query_groups == 0, "lga_attention_decode_window: bad head geometry");
-  LGA_CHECK_ARG(head_size == 128 && rope_n_elem == 128,
-                "lga_attention_decode_window: needs head_size == rope_n_elem == 128");
-  {
-    const int qpk = n_head / n_query_groups;
-    LGA_CHECK_ARG(qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8,
-                  "lga_attention_decode_window: q_per_kv must be 1, 2, 4 or 8");
-  }
-  LGA_CHECK_ARG(rope_rows > 0 && max_seq > 0, "lga_attention_decode_window: empty rope cache or kv cache");
-  LGA_CHECK_ARG(n_splits >= 1 && n_splits <= 256, "lga_attention_decode_window: n_splits must be in [1, 256]");
-  LGA_CHECK_ARG(n_splits == 1 || (workspace && counters),
-                "lga_attention_decode_window: split attention needs workspace + counters");
-  lga::window_append_kernel<128><<<dim3(n_query_groups, M), 64, 0, stream>>>(
-      (const uint16_t*)qkv, (uint16_t*)k_cache, (uint16_t*)v_cache, pos0, cos, sin, rope_rows, n_head, max_seq);
-  const int rc = lga::launch_hs<128, true, true>(qkv, k_cache, v_cache, pos0, y, workspace, counters, M, n_head,
-                                                 n_query_groups, max_seq, n_splits, scale, pos0, cos, sin, rope_rows,
-                                                 stream);
-  if (rc) return rc;
-  LGA_LAUNCH_RETURN();
+  return lga::attn_launch(AttnCall{"lga_attention_decode_window", lga::kWindow, false, M, qkv, k_cache, v_cache,
+                                   nullptr, nullptr, pos0, pos0, cos, sin, rope_rows, y, workspace, counters, 0, 0,
+                                   nullptr, n_head, n_query_groups, head_size, rope_n_elem, max_seq, n_splits, scale,
+                                   stream});
 }
 
 // The two decode forms over fp8 (e4m3) caches: k_codes / v_codes (G, max_seq, 128) uint8, k_scale / v_scale
 // (G, max_seq) fp32 powers of two. The new row(s) are quantized on the way in and scored as the cache holds them.
-#define LGA_KV8_COMMON(NAME)                                                                                         \
-  LGA_CHECK_ARG(n_query_groups > 0 && n_head % n_query_groups == 0, NAME ": bad head geometry");                     \
-  LGA_CHECK_ARG(head_size == 128 && rope_n_elem == 128, NAME ": needs head_size == rope_n_elem == 128");            \
-  {                                                                                                                  \
-    const int qpk = n_head / n_query_groups;                                                                         \
-    LGA_CHECK_ARG(qpk == 1 || qpk == 2 || qpk == 4 || qpk == 8, NAME ": q_per_kv must be 1, 2, 4 or 8");             \
-  }                                                                                                                  \
-  LGA_CHECK_ARG(rope_rows > 0 && max_seq > 0, NAME ": empty rope cache or kv cache");                                \
-  LGA_CHECK_ARG(n_splits >= 1 && n_splits <= 256, NAME ": n_splits must be in [1, 256]");                            \
-  LGA_CHECK_ARG(n_splits == 1 || (workspace && counters), NAME ": split attention needs workspace + counters")
-
 extern "C" int lga_attention_decode_fused_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale,
                                               float* v_scale, const int64_t* cache_pos, const int64_t* rope_pos,
                                               const float* cos, const float* sin, int rope_rows, void* y,
                                               float* workspace, unsigned* counters, int n_head, int n_query_groups,
                                               int head_size, int rope_n_elem, int max_seq, int n_splits, float scale,
                                               hipStream_t stream) {
-  LGA_CHECK_ARG(qkv && k_codes && v_codes && k_scale && v_scale && cache_pos && rope_pos && cos && sin && y,
-                "lga_attention_decode_fused_kv8: null pointer");
-  LGA_KV8_COMMON("lga_attention_decode_fused_kv8");
-  const int rc = lga::launch_hs<128, true, false, true>(qkv, k_codes, v_codes, cache_pos, y, workspace, counters, 1,
-                                                        n_head, n_query_groups, max_seq, n_splits, scale, rope_pos,
-                                                        cos, sin, rope_rows, stream, k_scale, v_scale);
-  if (rc) return rc;
-  LGA_LAUNCH_RETURN();
+  return lga::attn_launch(AttnCall{"lga_attention_decode_fused_kv8", lga::kOne, true, 1, qkv, k_codes, v_codes,
+                                   k_scale, v_scale, cache_pos, rope_pos, cos, sin, rope_rows, y, workspace, counters,
+                                   0, 0, nullptr, n_head, n_query_groups, head_size, rope_n_elem, max_seq, n_splits,
+                                   scale, stream});
 }
 
 extern "C" int lga_attention_decode_window_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale,
@@ -1336,18 +1098,10 @@ extern "C" int lga_attention_decode_window_kv8(const void* qkv, void* k_codes, v
                                                int rope_rows, void* y, float* workspace, unsigned* counters, int M,
                                                int n_head, int n_query_groups, int head_size, int rope_n_elem,
                                                int max_seq, int n_splits, float scale, hipStream_t stream) {
-  LGA_CHECK_ARG(qkv && k_codes && v_codes && k_scale && v_scale && pos0 && cos && sin && y,
-                "lga_attention_decode_window_kv8: null pointer");
-  LGA_CHECK_ARG(M >= 1 && M <= 8, "lga_attention_decode_window_kv8: M must be in [1, 8]");
-  LGA_KV8_COMMON("lga_attention_decode_window_kv8");
-  lga::window_append_kv8_kernel<<<dim3(n_query_groups, M), 64, 0, stream>>>(
-      (const uint16_t*)qkv, (uint8_t*)k_codes, (uint8_t*)v_codes, k_scale, v_scale, pos0, cos, sin, rope_rows, n_head,
-      max_seq);
-  const int rc = lga::launch_hs<128, true, true, true>(qkv, k_codes, v_codes, pos0, y, workspace, counters, M, n_head,
-                                                       n_query_groups, max_seq, n_splits, scale, pos0, cos, sin,
-                                                       rope_rows, stream, k_scale, v_scale);
-  if (rc) return rc;
-  LGA_LAUNCH_RETURN();
+  return lga::attn_launch(AttnCall{"lga_attention_decode_window_kv8", lga::kWindow, true, M, qkv, k_codes, v_codes,
+                                   k_scale, v_scale, pos0, pos0, cos, sin, rope_rows, y, workspace, counters, 0, 0,
+                                   nullptr, n_head, n_query_groups, head_size, rope_n_elem, max_seq, n_splits, scale,
+                                   stream});
 }
 
 // Batched decode step: B independent sequences in ONE launch, grid (n_splits, G * hsplit, B). Row b reads row b of
@@ -1362,21 +1116,10 @@ extern "C" int lga_attention_decode_batch(const void* qkv, void* k_cache, void* 
                                           const int32_t* active, int n_head, int n_query_groups, int head_size,
                                           int rope_n_elem, int max_seq, int n_splits, float scale,
                                           hipStream_t stream) {
-  LGA_CHECK_ARG(qkv && k_cache && v_cache && cache_pos && rope_pos && cos && sin && y,
-                "lga_attention_decode_batch: null pointer");
-  LGA_CHECK_ARG(B >= 1 && B <= 8, "lga_attention_decode_batch: B must be in [1, 8]");
-  LGA_KV8_COMMON("lga_attention_decode_batch");
-  LGA_CHECK_ARG(slot_stride >= (long long)n_query_groups * max_seq * head_size,
-                "lga_attention_decode_batch: slot_stride below one sequence's G * max_seq * head_size elements");
-  lga::BatchArgs ba;
-  ba.slot_stride = (long)slot_stride;
-  ba.active = active;
-  const int rc = lga::launch_hs<128, true, false, false, true>(qkv, k_cache, v_cache, cache_pos, y, workspace,
-                                                               counters, B, n_head, n_query_groups, max_seq, n_splits,
-                                                               scale, rope_pos, cos, sin, rope_rows, stream, nullptr,
-                                                               nullptr, ba);
-  if (rc) return rc;
-  LGA_LAUNCH_RETURN();
+  return lga::attn_launch(AttnCall{"lga_attention_decode_batch", lga::kBatch, false, B, qkv, k_cache, v_cache, nullptr,
+                                   nullptr, cache_pos, rope_pos, cos, sin, rope_rows, y, workspace, counters,
+                                   slot_stride, 0, active, n_head, n_query_groups, head_size, rope_n_elem, max_seq,
+                                   n_splits, scale, stream});
 }
 
 extern "C" int lga_attention_decode_batch_kv8(const void* qkv, void* k_codes, void* v_codes, float* k_scale,
@@ -1386,26 +1129,11 @@ extern "C" int lga_attention_decode_batch_kv8(const void* qkv, void* k_codes, vo
                                               long long scale_slot_stride, const int32_t* active, int n_head,
                                               int n_query_groups, int head_size, int rope_n_elem, int max_seq,
                                               int n_splits, float scale, hipStream_t stream) {
-  LGA_CHECK_ARG(qkv && k_codes && v_codes && k_scale && v_scale && cache_pos && rope_pos && cos && sin && y,
-                "lga_attention_decode_batch_kv8: null pointer");
-  LGA_CHECK_ARG(B >= 1 && B <= 8, "lga_attention_decode_batch_kv8: B must be in [1, 8]");
-  LGA_KV8_COMMON("lga_attention_decode_batch_kv8");
-  LGA_CHECK_ARG(slot_stride >= (long long)n_query_groups * max_seq * head_size,
-                "lga_attention_decode_batch_kv8: slot_stride below one sequence's G * max_seq * head_size codes");
-  LGA_CHECK_ARG(scale_slot_stride >= (long long)n_query_groups * max_seq,
-                "lga_attention_decode_batch_kv8: scale_slot_stride below one sequence's G * max_seq scales");
-  lga::BatchArgs ba;
-  ba.slot_stride = (long)slot_stride;
-  ba.scale_slot_stride = (long)scale_slot_stride;
-  ba.active = active;
-  const int rc = lga::launch_hs<128, true, false, true, true>(qkv, k_codes, v_codes, cache_pos, y, workspace, counters,
-                                                              B, n_head, n_query_groups, max_seq, n_splits, scale,
-                                                              rope_pos, cos, sin, rope_rows, stream, k_scale, v_scale,
-                                                              ba);
-  if (rc) return rc;
-  LGA_LAUNCH_RETURN();
+  return lga::attn_launch(AttnCall{"lga_attention_decode_batch_kv8", lga::kBatch, true, B, qkv, k_codes, v_codes,
+                                   k_scale, v_scale, cache_pos, rope_pos, cos, sin, rope_rows, y, workspace, counters,
+                                   slot_stride, scale_slot_stride, active, n_head, n_query_groups, head_size,
+                                   rope_n_elem, max_seq, n_splits, scale, stream});
 }
-#undef LGA_KV8_COMMON
 
 #ifdef LGA_ATTN_TRACE
 extern "C" int lga_attn_trace_read(unsigned long long* host, int n) {

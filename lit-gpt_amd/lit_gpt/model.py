@@ -124,8 +124,7 @@ class GPT(nn.Module):
         else:
             x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(1, T, -1)
         for block in self.transformer.h:
-            x = block(x, cos, sin, None, input_pos) if kv_slot == 0 else block(x, cos, sin, None, input_pos,
-                                                                              kv_slot=kv_slot)
+            x = block(x, cos, sin, None, input_pos, kv_slot=kv_slot)
         if last_token_only:
             x = x[:, -1:].contiguous()
         if hidden_only:
@@ -205,20 +204,27 @@ class GPT(nn.Module):
             raise TypeError("You need to call `gpt.set_kv_cache()`")
         if pos0.numel() != 1 or pos0.dtype != torch.int64 or pos0.device != idx.device:
             raise ValueError("pos0 must be one int64 position on the model's device")
+        return self._rows_step(idx, embedded, hidden_only,
+                               lambda attn, x, cos, sin, **kw: attn.decode_window(x, cos, sin, pos0, **kw)).view(M, -1)
+
+    def _rows_step(self, idx, embedded, hidden_only, attend) -> torch.Tensor:
+        """What the batched decode step and the verify window share: R = idx.numel() rows x (R, C), gathered here or
+        passed as ``embedded``; every block on the rows GEMVs with ``attend`` as its attention (``Block.decode_rows``);
+        then the last block's output (``hidden_only``) or ln_f fused into the rows lm_head -> (R, padded_vocab)."""
+        R, C = idx.numel(), self.transformer.wte.weight.shape[1]
         cos, sin = self._rope_tables()
-        C = self.transformer.wte.weight.shape[1]
         if embedded is not None:
-            if embedded.numel() != M * C or embedded.dtype != torch.bfloat16:
-                raise ValueError("embedded must hold M * n_embd bf16 values (the gathered wte rows of idx)")
-            x = embedded.view(M, C)
+            if embedded.numel() != R * C or embedded.dtype != torch.bfloat16:
+                raise ValueError(f"embedded must hold {R} * n_embd bf16 values (the gathered wte rows of idx)")
+            x = embedded.view(R, C)
         else:
-            x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(M, C)
+            x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(R, C)
         for block in self.transformer.h:
-            x = block.decode_window(x, cos, sin, pos0)
+            x = block.decode_rows(x, cos, sin, attend)
         if hidden_only:
             return x
         ln = self.transformer.ln_f
-        return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps, rows=True).view(M, -1)
+        return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps, rows=True)
 
     def _forward_batch(self, idx, input_pos, last_token_only, embedded, hidden_only, active=None) -> torch.Tensor:
         """The B > 1 forms of ``forward`` (its docstring). T = 1 per block: the rows qkv GEMV with norm_1 fused, the
@@ -246,22 +252,11 @@ class GPT(nn.Module):
         else:
             raise ValueError(f"input_pos must hold 1 (shared) or {B} (one per sequence) positions for a batched "
                              f"decode step, got shape {tuple(input_pos.shape)}")
-        cos, sin = self._rope_tables()
-        C = self.transformer.wte.weight.shape[1]
-        if embedded is not None:
-            if embedded.numel() != B * C or embedded.dtype != torch.bfloat16:
-                raise ValueError("embedded must hold B * n_embd bf16 values (the gathered wte rows of idx)")
-            x = embedded.view(B, C)
-        else:
-            x = ops.embedding(idx.reshape(-1).contiguous(), self.transformer.wte.weight).view(B, C)
         if active is not None and (active.numel() != B or active.dtype != torch.int32 or active.device != idx.device):
             raise ValueError(f"active must hold {B} int32 flags on the model's device")
-        for block in self.transformer.h:
-            x = block.decode_rows(x, cos, sin, pos) if active is None else block.decode_rows(x, cos, sin, pos, active)
-        if hidden_only:
-            return x.view(B, 1, C)
-        ln = self.transformer.ln_f
-        return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps, rows=True).view(B, 1, -1)
+        return self._rows_step(idx, embedded, hidden_only,
+                               lambda attn, x, cos, sin, **kw: attn.decode_rows(x, cos, sin, pos, active=active, **kw)
+                               ).view(B, 1, -1)
 
     @classmethod
     def from_name(cls, name: str, **kwargs: Any) -> "GPT":
@@ -323,34 +318,23 @@ class Block(nn.Module):
         self.mlp = config.mlp_class(config)
         self.config = config
 
-    def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
-                    active: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One batched decode step (GPT._forward_batch has checked the block): x (B, C), one token of each of B
-        sequences at ``pos`` (B,), on the multi-row GEMVs; row b has the bits of ``forward`` on that sequence.
-        ``active`` (B,) int32: rows flagged 0 are idle in the attention (``CausalSelfAttention.decode_rows``)."""
-        if active is None:
-            x = self.attn.decode_rows(x, cos, sin, pos, norm=self.norm_1, residual=x)
-        else:
-            x = self.attn.decode_rows(x, cos, sin, pos, norm=self.norm_1, residual=x, active=active)
-        g = quantize.swiglu(self.mlp.fc_1, self.mlp.fc_2, x, self.norm_2, rows=True)
-        return _lin(self.mlp.proj, g, residual=x, rows=True)
-
-    def decode_window(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor) -> torch.Tensor:
-        """One verify window (GPT.decode_window has checked the block): x (M, C), M consecutive tokens of one sequence
-        from ``pos0`` (1,); ``decode_rows`` with the window attention in place of the per-sequence launches."""
-        x = self.attn.decode_window(x, cos, sin, pos0, norm=self.norm_1, residual=x)
+    def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, attend) -> torch.Tensor:
+        """One multi-row decode step (GPT._rows_check has checked the block): x (R, C) on the multi-row GEMVs, one token
+        of each of R sequences or R consecutive tokens of one; row r has the bits of ``forward`` on that token.
+        ``attend`` is the step's attention, ``CausalSelfAttention.decode_rows`` or ``.decode_window`` bound to its
+        positions (``GPT._rows_step``)."""
+        x = attend(self.attn, x, cos, sin, norm=self.norm_1, residual=x)
         g = quantize.swiglu(self.mlp.fc_1, self.mlp.fc_2, x, self.norm_2, rows=True)
         return _lin(self.mlp.proj, g, residual=x, rows=True)
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor] = None,
                 input_pos: Optional[torch.Tensor] = None, *, kv_slot: int = 0) -> torch.Tensor:
         c = self.config
-        slot = {"kv_slot": kv_slot} if kv_slot else {}  # (slot 0: the attention call as it always was)
         if c.shared_attention_norm and not c.parallel_residual:
             raise NotImplementedError("No checkpoint amongst the ones we support uses this configuration"
                                       " (non-parallel residual and shared attention norm).")
         if c.parallel_residual:
-            return self._parallel_forward(x, cos, sin, mask, input_pos, **slot)
+            return self._parallel_forward(x, cos, sin, mask, input_pos, kv_slot)
         if not isinstance(self.norm_1, RMSNorm) or not isinstance(self.mlp, (LLaMAMLP, LLaMAMoE)):
             raise NotImplementedError(f"{type(self.mlp).__name__} / {type(self.norm_1).__name__} blocks have no "
                                       "MI355X kernels in this build")
@@ -366,11 +350,13 @@ class Block(nn.Module):
         ha = comm.tp_hook(self.attn)
         hm = comm.tp_hook(self.mlp)
         if ha is not None:
-            x = self.attn.forward(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x, reduce=ha, **slot)
+            x = self.attn.forward(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x, reduce=ha,
+                                  kv_slot=kv_slot)
         elif not self.attn._forward_hooks:
-            x = self.attn(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x, **slot)
+            x = self.attn(x, cos, sin, mask, input_pos, norm=self.norm_1, residual=x, kv_slot=kv_slot)
         else:
-            x = ops.add(self.attn(self.norm_1(x), cos, sin, mask, input_pos, **slot).contiguous(), x.contiguous())
+            x = ops.add(self.attn(self.norm_1(x), cos, sin, mask, input_pos, kv_slot=kv_slot).contiguous(),
+                        x.contiguous())
         if hm is not None and isinstance(self.mlp, LLaMAMLP):
             return self.mlp.forward(x, norm=self.norm_2, residual=x, reduce=hm)
         if hm is not None:
@@ -380,13 +366,13 @@ class Block(nn.Module):
         return ops.add(self.mlp(self.norm_2(x)).contiguous(), x)
 
 
-    def _parallel_forward(self, x, cos, sin, mask, input_pos, **slot) -> torch.Tensor:
+    def _parallel_forward(self, x, cos, sin, mask, input_pos, kv_slot) -> torch.Tensor:
         """GPT-NeoX block (reference model.py:572-593, parallel_residual): n_1 = norm_1(x), h = attn(n_1),
         n_2 = n_1 if shared_attention_norm else norm_2(x), x = mlp(n_2) + h + x — the reference's association:
         bf16(mlp + h) (fused into the mlp.proj epilogue) then + x. Under tensor parallelism the attn / mlp outputs
         go through their all-reduce hooks first (generate/tp.py), as in the reference."""
         n_1 = self.norm_1(x)
-        h = self.attn(n_1, cos, sin, mask, input_pos, **slot).contiguous()
+        h = self.attn(n_1, cos, sin, mask, input_pos, kv_slot=kv_slot).contiguous()
         n_2 = n_1 if self.config.shared_attention_norm else self.norm_2(x)
         if self.mlp._forward_hooks:  # TP: the hook must see the mlp output alone
             m = ops.add(self.mlp(n_2).contiguous(), h)
@@ -423,79 +409,96 @@ class CausalSelfAttention(nn.Module):
         dev = x.device
         if input_pos is None:
             # no cache (training-style causal forward, model.py:510-513): a private cache of T rows
-            pos = torch.arange(T, device=dev, dtype=torch.int64)
+            pos = rope_pos = torch.arange(T, device=dev, dtype=torch.int64)
             kc = torch.empty(G, T, hs, dtype=qkv.dtype, device=dev)  # bf16, or fp32 under --precision 32-true
-            vc = torch.empty_like(kc)
-            rope_pos = pos
+            cache = (kc, torch.empty_like(kc))
         else:
             if not isinstance(self.kv_cache, KVCache):
                 raise TypeError("You need to call `gpt.set_kv_cache()`")
-            kv = self.kv_cache
-            if not kv.fp8 and kv.k.dtype != qkv.dtype:  # reference KVCache.forward casts to the activation dtype (:790-791)
-                kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
-            if not 0 <= kv_slot < kv.k.size(0):
-                raise ValueError(f"kv_slot {kv_slot}: the KV cache holds {kv.k.size(0)} sequence(s)")
-            kc, vc = (kv.k, kv.v) if kv.k.size(0) == 1 else (kv.k[kv_slot], kv.v[kv_slot])
-            kv8 = kv.slot(kv_slot) if kv.fp8 else None
+            if not 0 <= kv_slot < self.kv_cache.k.size(0):
+                raise ValueError(f"kv_slot {kv_slot}: the KV cache holds {self.kv_cache.k.size(0)} sequence(s)")
+            cache = self._cache(qkv.dtype, kv_slot)
             pos = input_pos
             # callers may pass the full cos/sin tables (our GPT.forward) or rows pre-selected by input_pos (the
             # reference's GPT.forward, model.py:505-506)
-            rope_pos = pos if (cos.size(0) != T or T == kc.size(-2)) else torch.arange(T, device=dev)
-        if input_pos is not None and kv8 is not None:
-            y = self._attend_kv8(qkv, kv8, pos, rope_pos, cos, sin)
-        else:
-            y = self._attend(qkv, kc, vc, pos, rope_pos, cos, sin)
+            rope_pos = pos if (cos.size(0) != T or T == cache[0].size(-2)) else torch.arange(T, device=dev)
+        y = self._attend(qkv, cache, pos, rope_pos, cos, sin)
         out = _lin(self.proj, y.view(1, T, H * hs), residual=residual, reduce=reduce)
         return out.view(B, T, -1)
 
-    def _attend(self, qkv, kc, vc, pos, rope_pos, cos, sin, out=None) -> torch.Tensor:
-        """RoPE + KV-append + causal attention of the T rows of ``qkv`` over one sequence's caches -> (T, H * hs)."""
+    def _cache(self, dtype: torch.dtype, slot: Optional[int] = None):
+        """The KV cache as the ops take it, of sequence ``slot`` or (None) of all slots: (k, v), cast to the activation
+        ``dtype`` as the reference's KVCache.forward does (:790-791), or (k codes, v codes, k scales, v scales)."""
+        kv = self.kv_cache
+        if kv.fp8:
+            whole = (kv.k, kv.v, kv.k_scale, kv.v_scale)
+        else:
+            if kv.k.dtype != dtype:
+                kv.k, kv.v = kv.k.to(dtype), kv.v.to(dtype)
+            whole = (kv.k, kv.v)
+        return whole if slot is None else tuple(t[slot] for t in whole)
+
+    def _decode_setup(self, qkv, cache, cos, sin, split=True):
+        """What every attention call on decode rows needs: the fp32 contiguous rope tables, the split count of the
+        one-row step on this cache length (the bits of y depend on it) and the split workspace for qkv's row count.
+        One ``AttentionWorkspace`` per row count serves every form (one row, window, batch) and both cache formats:
+        all launches are serial on one stream and the last-arriving workgroup of each re-arms the counters, so a
+        launch always finds them as the constructor left them."""
         c = self.config
         H, G, hs = c.n_head, c.n_query_groups, c.head_size
-        T, dev = qkv.size(0), qkv.device
+        rows, dev = qkv.size(0), qkv.device
         cos = cos.to(device=dev, dtype=torch.float32).contiguous()
         sin = sin.to(device=dev, dtype=torch.float32).contiguous()
-        S = kc.size(-2)
-        ws = None
-        n_splits = 1
-        if T == 1 and qkv.dtype == torch.bfloat16:
-            n_splits = ops.decode_splits(G, H // G, hs, S)
-            ws = getattr(self, "_attn_ws", None)
-            if ws is None or ws.key != (1, H, G, hs, n_splits) or ws.counters.device != dev:
-                ws = self._attn_ws = ops.AttentionWorkspace(1, H, G, hs, n_splits, dev)
-        if T == 1 and self.fuse_decode and ops.decode_fusable(hs, c.rope_n_elem) and qkv.dtype == torch.bfloat16:
+        if not split:
+            return cos, sin, 1, None
+        n_splits = ops.decode_splits(G, H // G, hs, cache[0].size(-2))
+        wss = self.__dict__.setdefault("_decode_ws", {})
+        ws = wss.get(rows)
+        if ws is None or ws.key != (rows, H, G, hs, n_splits) or ws.counters.device != dev:
+            ws = wss[rows] = ops.AttentionWorkspace(rows, H, G, hs, n_splits, dev)
+        return cos, sin, n_splits, ws
+
+    def _decode_attention(self, form, qkv, cache, pos, rope_pos, cos, sin, active=None, out=None) -> torch.Tensor:
+        """RoPE + KV-append + split decode attention of the rows of ``qkv`` in one launch of the form ``form`` ("fused",
+        "window" or "batch": ``ops._attention_decode``) over ``cache`` (``_cache``) -> (rows, H * hs)."""
+        c = self.config
+        cos, sin, n_splits, ws = self._decode_setup(qkv, cache, cos, sin)
+        return ops._attention_decode(form, qkv, cache, pos, rope_pos, cos, sin, c.n_head, c.n_query_groups, c.head_size,
+                                     c.rope_n_elem, 1.0 / math.sqrt(c.head_size), n_splits, ws, out, active)
+
+    def _attend(self, qkv, cache, pos, rope_pos, cos, sin, out=None) -> torch.Tensor:
+        """RoPE + KV-append + causal attention of the T rows of ``qkv`` over one sequence's ``cache`` -> (T, H * hs)."""
+        c = self.config
+        H, G, hs = c.n_head, c.n_query_groups, c.head_size
+        if len(cache) == 4:
+            return self._attend_kv8(qkv, cache, pos, rope_pos, cos, sin, out)
+        decode = qkv.size(0) == 1 and qkv.dtype == torch.bfloat16
+        if decode and self.fuse_decode and ops.decode_fusable(hs, c.rope_n_elem):
             # decode token: RoPE + KV-append + attention in a single launch
-            return ops.attention_decode_fused(qkv, kc, vc, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem,
-                                              1.0 / math.sqrt(hs), n_splits, workspace=ws, out=out)
-        q = ops.rope_kv_append(qkv, kc, vc, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem)
-        return ops.attention(q, kc, vc, pos, H, G, hs, 1.0 / math.sqrt(hs), n_splits, workspace=ws, out=out)
+            return self._decode_attention("fused", qkv, cache, pos, rope_pos, cos, sin, out=out)
+        cos, sin, n_splits, ws = self._decode_setup(qkv, cache, cos, sin, split=decode)
+        q = ops.rope_kv_append(qkv, *cache, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem)
+        return ops.attention(q, *cache, pos, H, G, hs, 1.0 / math.sqrt(hs), n_splits, workspace=ws, out=out)
 
     def _attend_kv8(self, qkv, cache, pos, rope_pos, cos, sin, out=None) -> torch.Tensor:
-        """``_attend`` over one sequence's fp8 cache (``KVCache.slot``). Every row is scored as the cache holds it, the
-        call's own rows included. T = 1: quantizing append + attention in one launch. T > 1: the quantizing append,
-        the cache expanded into the model's bf16 scratch pair, then the bf16 prefill attention over that (no host read
-        of ``pos``: graph-safe)."""
+        """``_attend`` over one sequence's fp8 cache. Every row is scored as the cache holds it, the call's own rows
+        included. T = 1: quantizing append + attention in one launch. T > 1: the quantizing append, the cache expanded
+        into the model's bf16 scratch pair, then the bf16 prefill attention over that (no host read of ``pos``:
+        graph-safe)."""
         c = self.config
         H, G, hs = c.n_head, c.n_query_groups, c.head_size
-        T, dev = qkv.size(0), qkv.device
         if qkv.dtype != torch.bfloat16:
             raise NotImplementedError(f"an fp8 KV cache with {qkv.dtype} activations: the kernels take bf16")
-        cos = cos.to(device=dev, dtype=torch.float32).contiguous()
-        sin = sin.to(device=dev, dtype=torch.float32).contiguous()
-        scale = 1.0 / math.sqrt(hs)
-        if T == 1:
-            n_splits = ops.decode_splits(G, H // G, hs, cache[0].size(-2))
-            ws = getattr(self, "_attn_ws", None)
-            if ws is None or ws.key != (1, H, G, hs, n_splits) or ws.counters.device != dev:
-                ws = self._attn_ws = ops.AttentionWorkspace(1, H, G, hs, n_splits, dev)
-            return ops.attention_decode_fused_kv8(qkv, cache, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem, scale,
-                                                  n_splits, workspace=ws, out=out)
+        if qkv.size(0) == 1:
+            return self._decode_attention("fused", qkv, cache, pos, rope_pos, cos, sin, out=out)
+        dev = qkv.device
+        cos, sin, _, _ = self._decode_setup(qkv, cache, cos, sin, split=False)
         q = ops.kv8_rope_append(qkv, cache, pos, rope_pos, cos, sin, H, G, hs, c.rope_n_elem)
         kv = self.kv_cache
         if kv.scratch is None or kv.scratch[0].shape != cache[0].shape or kv.scratch[0].device != dev:
             kv.scratch = tuple(torch.empty(cache[0].shape, dtype=torch.bfloat16, device=dev) for _ in range(2))
         kd, vd = ops.kv8_dequantize(cache, out=kv.scratch)
-        return ops.attention(q, kd, vd, pos, H, G, hs, scale, 1, out=out)
+        return ops.attention(q, kd, vd, pos, H, G, hs, 1.0 / math.sqrt(hs), 1, out=out)
 
     def batch_fusable(self, dtype: torch.dtype) -> bool:
         """Whether ``ops.attention_decode_batch`` covers this module: the fused decode form's geometry, bf16."""
@@ -512,41 +515,19 @@ class CausalSelfAttention(nn.Module):
         is the one-sequence step's, the bits of y depend on it), otherwise the one-sequence decode attention once per
         sequence, all through the one ``AttentionWorkspace`` (serial launches; its counters re-arm). ``active`` (B,)
         int32 marks idle rows (0): their cache slot is untouched and their y is zero — the batch launch only."""
-        c = self.config
-        H, G, hs = c.n_head, c.n_query_groups, c.head_size
         B = x.size(0)
-        kv = self.kv_cache
         qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
-        if not kv.fp8 and kv.k.dtype != qkv.dtype:
-            kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
         fusable = self.batch_fusable(qkv.dtype)
         if active is not None and not fusable:
             raise NotImplementedError("idle rows (active) need the batched decode attention launch: head_size == "
                                       "rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group, bf16 activations")
         if fusable and (batch_attention or active is not None):
-            dev = qkv.device
-            n_splits = ops.decode_splits(G, H // G, hs, kv.k.size(-2))
-            wss = self.__dict__.setdefault("_batch_ws", {})
-            ws = wss.get(B)
-            if ws is None or ws.key != (B, H, G, hs, n_splits) or ws.counters.device != dev:
-                ws = wss[B] = ops.AttentionWorkspace(B, H, G, hs, n_splits, dev)
-            cos = cos.to(device=dev, dtype=torch.float32).contiguous()
-            sin = sin.to(device=dev, dtype=torch.float32).contiguous()
-            if kv.fp8:
-                y = ops.attention_decode_batch_kv8(qkv, (kv.k, kv.v, kv.k_scale, kv.v_scale), pos, cos, sin, H, G, hs,
-                                                   c.rope_n_elem, 1.0 / math.sqrt(hs), n_splits, workspace=ws,
-                                                   active=active)
-            else:
-                y = ops.attention_decode_batch(qkv, kv.k, kv.v, pos, cos, sin, H, G, hs, c.rope_n_elem,
-                                               1.0 / math.sqrt(hs), n_splits, workspace=ws, active=active)
-            return _lin(self.proj, y, residual=residual, rows=True)
-        y = torch.empty(B, c.n_head * c.head_size, dtype=qkv.dtype, device=qkv.device)
-        for b in range(B):
-            p = pos[b:b + 1]
-            if kv.fp8:
-                self._attend_kv8(qkv[b:b + 1], kv.slot(b), p, p, cos, sin, out=y[b:b + 1])
-            else:
-                self._attend(qkv[b:b + 1], kv.k[b], kv.v[b], p, p, cos, sin, out=y[b:b + 1])
+            y = self._decode_attention("batch", qkv, self._cache(qkv.dtype), pos, pos, cos, sin, active=active)
+        else:
+            y = torch.empty(B, self.config.n_head * self.config.head_size, dtype=qkv.dtype, device=qkv.device)
+            for b in range(B):
+                p = pos[b:b + 1]
+                self._attend(qkv[b:b + 1], self._cache(qkv.dtype, b), p, p, cos, sin, out=y[b:b + 1])
         return _lin(self.proj, y, residual=residual, rows=True)
 
     def decode_window(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor, *,
@@ -555,27 +536,8 @@ class CausalSelfAttention(nn.Module):
         (1,). The qkv and the out-projection are the multi-row GEMVs; the M rows read one K / V, so attention is ONE
         ``ops.attention_decode_window`` call with the split count of the one-row step (``ops.decode_splits`` of the
         cache length: the bits of y depend on it, so the cache must be as long as the one ``generate`` would use)."""
-        c = self.config
-        H, G, hs = c.n_head, c.n_query_groups, c.head_size
-        M, dev = x.size(0), x.device
-        kv = self.kv_cache
         qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
-        if not kv.fp8 and kv.k.dtype != qkv.dtype:
-            kv.k, kv.v = kv.k.to(qkv.dtype), kv.v.to(qkv.dtype)
-        kc, vc = kv.k[0], kv.v[0]
-        n_splits = ops.decode_splits(G, H // G, hs, kc.size(-2))
-        wss = self.__dict__.setdefault("_window_ws", {})
-        ws = wss.get(M)
-        if ws is None or ws.key != (M, H, G, hs, n_splits) or ws.counters.device != dev:
-            ws = wss[M] = ops.AttentionWorkspace(M, H, G, hs, n_splits, dev)
-        cos = cos.to(device=dev, dtype=torch.float32).contiguous()
-        sin = sin.to(device=dev, dtype=torch.float32).contiguous()
-        if kv.fp8:
-            y = ops.attention_decode_window_kv8(qkv, kv.slot(0), pos0, cos, sin, H, G, hs, c.rope_n_elem,
-                                                1.0 / math.sqrt(hs), n_splits, workspace=ws)
-        else:
-            y = ops.attention_decode_window(qkv, kc, vc, pos0, cos, sin, H, G, hs, c.rope_n_elem,
-                                            1.0 / math.sqrt(hs), n_splits, workspace=ws)
+        y = self._decode_attention("window", qkv, self._cache(qkv.dtype, 0), pos0, None, cos, sin)
         return _lin(self.proj, y, residual=residual, rows=True)
 
     def scaled_dot_product_attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,

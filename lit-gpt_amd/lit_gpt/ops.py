@@ -629,31 +629,96 @@ def attention(q, k_cache, v_cache, input_pos, n_head, n_query_groups, head_size,
     return y
 
 
+MAX_WINDOW_ROWS = 8  # rows per lga_attention_decode_window / lga_spec_accept launch
+MAX_BATCH_ROWS = 8  # sequences per lga_attention_decode_batch launch (the rows GEMVs' MAX_GEMV_ROWS)
+
+
+# ------------------------------------------------------------------------------------------ fp8 (e4m3) KV cache
+# One sequence's cache is (k_codes, v_codes, k_scale, v_scale): codes (G, max_seq, 128) uint8, scales (G, max_seq)
+# fp32 powers of two (include/litgpt_amd.h states the format); the batch forms take all slots at once, one more
+# leading dimension on each.
+def _kv8(cache, name, dims=3):
+    kc, vc, ks, vs = cache
+    if (kc.shape != vc.shape or kc.dim() != dims or kc.shape[-1] != 128 or ks.shape != kc.shape[:-1]
+            or vs.shape != ks.shape):
+        lead = "(G" if dims == 3 else "(slots, G"
+        raise ValueError(f"{name}: an fp8 cache is codes {lead}, max_seq, 128) uint8 x 2 and scales {lead}, max_seq) "
+                         f"fp32 x 2, got {tuple(kc.shape)}, {tuple(vc.shape)}, {tuple(ks.shape)}, {tuple(vs.shape)}")
+    return (_dev(kc, "k_codes", torch.uint8), _dev(vc, "v_codes", torch.uint8), _dev(ks, "k_scale", torch.float32),
+            _dev(vs, "v_scale", torch.float32))
+
+
+def _attention_decode(form, qkv, cache, pos, rope_pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale,
+                      n_splits, workspace, out, active=None):
+    """The six ``attention_decode_*`` functions: ``form`` is "fused" (one row), "window" (M rows of one sequence from
+    ``pos`` (1,)) or "batch" (B sequences, ``pos`` (B,), the caches of all slots); ``cache`` is (k, v) bf16 or (k codes,
+    v codes, k scales, v scales) fp8. Checks, workspace, one ``lga_attention_decode_*`` call; returns y."""
+    H, G, hs = n_head, n_query_groups, head_size
+    fp8 = len(cache) == 4
+    name = f"attention_decode_{form}" + ("_kv8" if fp8 else "")
+    rows, kc = qkv.shape[0], cache[0]
+    R = {"fused": "T", "window": "M", "batch": "B"}[form]
+    if form == "fused":
+        if rows != 1:
+            raise ValueError(f"{name} handles exactly one token (T = 1)")
+    else:
+        cap = MAX_WINDOW_ROWS if form == "window" else MAX_BATCH_ROWS
+        if qkv.dim() != 2 or not 1 <= rows <= cap:
+            raise ValueError(f"{name}: qkv must be ({R}, (H + 2G) * hs) with 1 <= {R} <= {cap}, got "
+                             f"{tuple(qkv.shape)}")
+        if qkv.shape[1] != (H + 2 * G) * hs:
+            raise ValueError(f"{name}: qkv rows must hold (H + 2G) * hs values")
+    if form == "window" and pos.numel() != 1:
+        raise ValueError(f"{name}: pos0 holds one position (row r sits at pos0 + r)")
+    if form == "batch":
+        if kc.dim() != 4 or kc.shape[0] < rows or kc.shape[1] != G:
+            raise ValueError(f"{name}: the caches are the whole (slots >= B, G, max_seq, hs) tensors, got "
+                             f"{tuple(kc.shape)} for B = {rows}")
+        if pos.numel() != rows:
+            raise ValueError(f"{name}: pos holds one position per sequence ({rows}), got {tuple(pos.shape)}")
+        if active is not None and (active.numel() != rows or active.dtype != torch.int32):
+            raise ValueError(f"{name}: active must hold {rows} int32 flags")
+        if cache[1].shape != kc.shape:
+            raise ValueError(f"{name}: k_cache and v_cache must have one shape")
+    if fp8:
+        ptrs = _kv8(cache, name, 4 if form == "batch" else 3)
+    else:
+        ptrs = _dev(kc, "k_cache", torch.bfloat16), _dev(cache[1], "v_cache", torch.bfloat16)
+    y = out if out is not None else torch.empty(rows, H * hs, dtype=torch.bfloat16, device=qkv.device)
+    if y.numel() != rows * H * hs:
+        raise ValueError(f"{name}: out must hold ({R}, H * hs) values")
+    ws = cnt = None
+    if n_splits > 1:
+        key = (rows, H, G, hs, n_splits)
+        if form == "fused":  # the one-row forms build what they need
+            if workspace is None or workspace.key != key:
+                workspace = AttentionWorkspace(*key, qkv.device)
+        elif workspace is None:
+            raise ValueError(f"{name}: split attention needs an AttentionWorkspace({R}, ...)")
+        elif workspace.key != key:
+            raise ValueError(f"{name}: workspace built for {workspace.key}, the call needs {key}")
+        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
+    args = [_dev(qkv, "qkv", torch.bfloat16), *ptrs, _dev(pos, "pos", torch.int64)]
+    if form != "window":  # (a window's rope positions are its cache positions, pos0 + r)
+        args.append(_dev(rope_pos, "rope_pos", torch.int64))
+    args += [_dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32), cos.shape[0],
+             _dev(y, "y", torch.bfloat16), ws, cnt]
+    if form != "fused":
+        args.append(rows)
+    if form == "batch":  # the slot strides (of the scale rows too), the idle flags
+        args += [kc.stride(0)] + ([cache[2].stride(0)] if fp8 else []) + [_opt(active, "active", torch.int32)]
+    _check(getattr(load_library(), "lga_" + name)(*args, H, G, hs, rope_n_elem, kc.shape[-2], n_splits, float(scale),
+                                                  _stream()))
+    return y
+
+
 def attention_decode_fused(qkv, k_cache, v_cache, cache_pos, rope_pos, cos, sin, n_head, n_query_groups,
                            head_size, rope_n_elem, scale, n_splits=1, workspace: Optional[AttentionWorkspace] = None,
                            out=None):
     """One decode token: RoPE + KV-append + attention in one launch. qkv (1, (H+2G)*hs) is the fused projection
     row; returns y (1, H*hs) and leaves roped k / v stored in the caches at cache_pos[0]."""
-    if qkv.shape[0] != 1:
-        raise ValueError("attention_decode_fused handles exactly one token (T = 1)")
-    max_seq = k_cache.shape[-2]
-    y = out if out is not None else torch.empty(1, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
-    if n_splits > 1:
-        if workspace is None or workspace.key != (1, n_head, n_query_groups, head_size, n_splits):
-            workspace = AttentionWorkspace(1, n_head, n_query_groups, head_size, n_splits, qkv.device)
-        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
-    else:
-        ws = cnt = None
-    _check(load_library().lga_attention_decode_fused(
-        _dev(qkv, "qkv", torch.bfloat16), _dev(k_cache, "k_cache", torch.bfloat16),
-        _dev(v_cache, "v_cache", torch.bfloat16), _dev(cache_pos, "cache_pos", torch.int64),
-        _dev(rope_pos, "rope_pos", torch.int64), _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32),
-        cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, n_head, n_query_groups, head_size, rope_n_elem, max_seq,
-        n_splits, float(scale), _stream()))
-    return y
-
-
-MAX_WINDOW_ROWS = 8  # rows per lga_attention_decode_window / lga_spec_accept launch
+    return _attention_decode("fused", qkv, (k_cache, v_cache), cache_pos, rope_pos, cos, sin, n_head, n_query_groups,
+                             head_size, rope_n_elem, scale, n_splits, workspace, out)
 
 
 def attention_decode_window(qkv, k_cache, v_cache, pos0, cos, sin, n_head, n_query_groups, head_size, rope_n_elem,
@@ -661,45 +726,8 @@ def attention_decode_window(qkv, k_cache, v_cache, pos0, cos, sin, n_head, n_que
     """A speculative verify window: M = qkv.shape[0] (1..8) rows of ONE sequence at positions pos0[0] + r. RoPE +
     KV-append + decode attention; y (M, H*hs) and the caches end bit-identical to M successive
     ``attention_decode_fused`` calls with the same ``n_splits``. ``pos0`` (1,) int64 is read on the device."""
-    M = qkv.shape[0]
-    if qkv.dim() != 2 or not 1 <= M <= MAX_WINDOW_ROWS:
-        raise ValueError(f"attention_decode_window: qkv must be (M, (H + 2G) * hs) with 1 <= M <= {MAX_WINDOW_ROWS}, "
-                         f"got {tuple(qkv.shape)}")
-    if qkv.shape[1] != (n_head + 2 * n_query_groups) * head_size:
-        raise ValueError("attention_decode_window: qkv rows must hold (H + 2G) * hs values")
-    if pos0.numel() != 1:
-        raise ValueError("attention_decode_window: pos0 holds one position (row r sits at pos0 + r)")
-    max_seq = k_cache.shape[-2]
-    y = out if out is not None else torch.empty(M, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
-    if y.numel() != M * n_head * head_size:
-        raise ValueError("attention_decode_window: out must hold (M, H * hs) values")
-    if n_splits > 1:
-        if workspace is None:
-            raise ValueError("attention_decode_window: split attention needs an AttentionWorkspace(M, ...)")
-        if workspace.key != (M, n_head, n_query_groups, head_size, n_splits):
-            raise ValueError(f"attention_decode_window: workspace built for {workspace.key}, the call needs "
-                             f"{(M, n_head, n_query_groups, head_size, n_splits)}")
-        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
-    else:
-        ws = cnt = None
-    _check(load_library().lga_attention_decode_window(
-        _dev(qkv, "qkv", torch.bfloat16), _dev(k_cache, "k_cache", torch.bfloat16),
-        _dev(v_cache, "v_cache", torch.bfloat16), _dev(pos0, "pos0", torch.int64), _dev(cos, "cos", torch.float32),
-        _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, M, n_head,
-        n_query_groups, head_size, rope_n_elem, max_seq, n_splits, float(scale), _stream()))
-    return y
-
-
-# ------------------------------------------------------------------------------------------ fp8 (e4m3) KV cache
-# One sequence's cache is (k_codes, v_codes, k_scale, v_scale): codes (G, max_seq, 128) uint8, scales (G, max_seq)
-# fp32 powers of two (include/litgpt_amd.h states the format). The four wrappers mirror their bf16 twins.
-def _kv8(cache, name):
-    kc, vc, ks, vs = cache
-    if kc.shape != vc.shape or kc.dim() != 3 or kc.shape[-1] != 128 or ks.shape != kc.shape[:2] or vs.shape != ks.shape:
-        raise ValueError(f"{name}: an fp8 cache is codes (G, max_seq, 128) uint8 x 2 and scales (G, max_seq) fp32 x 2, "
-                         f"got {tuple(kc.shape)}, {tuple(vc.shape)}, {tuple(ks.shape)}, {tuple(vs.shape)}")
-    return (_dev(kc, "k_codes", torch.uint8), _dev(vc, "v_codes", torch.uint8), _dev(ks, "k_scale", torch.float32),
-            _dev(vs, "v_scale", torch.float32))
+    return _attention_decode("window", qkv, (k_cache, v_cache), pos0, None, cos, sin, n_head, n_query_groups,
+                             head_size, rope_n_elem, scale, n_splits, workspace, out)
 
 
 def kv8_rope_append(qkv, cache, cache_pos, rope_pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem,
@@ -737,87 +765,16 @@ def attention_decode_fused_kv8(qkv, cache, cache_pos, rope_pos, cos, sin, n_head
                                out=None):
     """``attention_decode_fused`` over an fp8 cache: the new row is quantized into the cache at cache_pos[0] and every
     key and value, the new one included, is read as the cache holds it."""
-    if qkv.shape[0] != 1:
-        raise ValueError("attention_decode_fused_kv8 handles exactly one token (T = 1)")
-    ptrs = _kv8(cache, "attention_decode_fused_kv8")
-    y = out if out is not None else torch.empty(1, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
-    if n_splits > 1:
-        if workspace is None or workspace.key != (1, n_head, n_query_groups, head_size, n_splits):
-            workspace = AttentionWorkspace(1, n_head, n_query_groups, head_size, n_splits, qkv.device)
-        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
-    else:
-        ws = cnt = None
-    _check(load_library().lga_attention_decode_fused_kv8(
-        _dev(qkv, "qkv", torch.bfloat16), *ptrs, _dev(cache_pos, "cache_pos", torch.int64),
-        _dev(rope_pos, "rope_pos", torch.int64), _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32),
-        cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, n_head, n_query_groups, head_size, rope_n_elem,
-        cache[0].shape[-2], n_splits, float(scale), _stream()))
-    return y
+    return _attention_decode("fused", qkv, tuple(cache), cache_pos, rope_pos, cos, sin, n_head, n_query_groups,
+                             head_size, rope_n_elem, scale, n_splits, workspace, out)
 
 
 def attention_decode_window_kv8(qkv, cache, pos0, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale,
                                 n_splits=1, workspace: Optional[AttentionWorkspace] = None, out=None):
     """``attention_decode_window`` over an fp8 cache: y (M, H*hs), codes and scales bit-identical to M successive
     ``attention_decode_fused_kv8`` calls with the same ``n_splits``."""
-    M = qkv.shape[0]
-    if qkv.dim() != 2 or not 1 <= M <= MAX_WINDOW_ROWS:
-        raise ValueError(f"attention_decode_window_kv8: qkv must be (M, (H + 2G) * hs) with 1 <= M <= "
-                         f"{MAX_WINDOW_ROWS}, got {tuple(qkv.shape)}")
-    if qkv.shape[1] != (n_head + 2 * n_query_groups) * head_size:
-        raise ValueError("attention_decode_window_kv8: qkv rows must hold (H + 2G) * hs values")
-    if pos0.numel() != 1:
-        raise ValueError("attention_decode_window_kv8: pos0 holds one position (row r sits at pos0 + r)")
-    ptrs = _kv8(cache, "attention_decode_window_kv8")
-    y = out if out is not None else torch.empty(M, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
-    if y.numel() != M * n_head * head_size:
-        raise ValueError("attention_decode_window_kv8: out must hold (M, H * hs) values")
-    if n_splits > 1:
-        if workspace is None:
-            raise ValueError("attention_decode_window_kv8: split attention needs an AttentionWorkspace(M, ...)")
-        if workspace.key != (M, n_head, n_query_groups, head_size, n_splits):
-            raise ValueError(f"attention_decode_window_kv8: workspace built for {workspace.key}, the call needs "
-                             f"{(M, n_head, n_query_groups, head_size, n_splits)}")
-        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
-    else:
-        ws = cnt = None
-    _check(load_library().lga_attention_decode_window_kv8(
-        _dev(qkv, "qkv", torch.bfloat16), *ptrs, _dev(pos0, "pos0", torch.int64), _dev(cos, "cos", torch.float32),
-        _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16), ws, cnt, M, n_head,
-        n_query_groups, head_size, rope_n_elem, cache[0].shape[-2], n_splits, float(scale), _stream()))
-    return y
-
-
-MAX_BATCH_ROWS = 8  # sequences per lga_attention_decode_batch launch (the rows GEMVs' MAX_GEMV_ROWS)
-
-
-def _batch_args(name, qkv, k_cache, pos, n_head, n_query_groups, head_size, n_splits, workspace, active, out):
-    """The checks the two batch forms share; returns (B, y, ws, cnt, active pointer)."""
-    B = qkv.shape[0]
-    if qkv.dim() != 2 or not 1 <= B <= MAX_BATCH_ROWS:
-        raise ValueError(f"{name}: qkv must be (B, (H + 2G) * hs) with 1 <= B <= {MAX_BATCH_ROWS}, got "
-                         f"{tuple(qkv.shape)}")
-    if qkv.shape[1] != (n_head + 2 * n_query_groups) * head_size:
-        raise ValueError(f"{name}: qkv rows must hold (H + 2G) * hs values")
-    if k_cache.dim() != 4 or k_cache.shape[0] < B or k_cache.shape[1] != n_query_groups:
-        raise ValueError(f"{name}: the caches are the whole (slots >= B, G, max_seq, hs) tensors, got "
-                         f"{tuple(k_cache.shape)} for B = {B}")
-    if pos.numel() != B:
-        raise ValueError(f"{name}: pos holds one position per sequence ({B}), got {tuple(pos.shape)}")
-    if active is not None and (active.numel() != B or active.dtype != torch.int32):
-        raise ValueError(f"{name}: active must hold {B} int32 flags")
-    y = out if out is not None else torch.empty(B, n_head * head_size, dtype=torch.bfloat16, device=qkv.device)
-    if y.numel() != B * n_head * head_size:
-        raise ValueError(f"{name}: out must hold (B, H * hs) values")
-    if n_splits > 1:
-        if workspace is None:
-            raise ValueError(f"{name}: split attention needs an AttentionWorkspace(B, ...)")
-        if workspace.key != (B, n_head, n_query_groups, head_size, n_splits):
-            raise ValueError(f"{name}: workspace built for {workspace.key}, the call needs "
-                             f"{(B, n_head, n_query_groups, head_size, n_splits)}")
-        ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
-    else:
-        ws = cnt = None
-    return B, y, ws, cnt, _opt(active, "active", torch.int32)
+    return _attention_decode("window", qkv, tuple(cache), pos0, None, cos, sin, n_head, n_query_groups, head_size,
+                             rope_n_elem, scale, n_splits, workspace, out)
 
 
 def attention_decode_batch(qkv, k_cache, v_cache, pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem,
@@ -827,18 +784,8 @@ def attention_decode_batch(qkv, k_cache, v_cache, pos, cos, sin, n_head, n_query
     int64 read on the device). y (B, H*hs) and slot b end bit-identical to ``attention_decode_fused`` on that row and
     slot with the same ``n_splits``. ``active`` (B,) int32: a row with active[b] == 0 is idle (y[b] = 0, slot b
     untouched); None runs every row."""
-    name = "attention_decode_batch"
-    B, y, ws, cnt, act = _batch_args(name, qkv, k_cache, pos, n_head, n_query_groups, head_size, n_splits, workspace,
-                                     active, out)
-    if v_cache.shape != k_cache.shape:
-        raise ValueError(f"{name}: k_cache and v_cache must have one shape")
-    _check(load_library().lga_attention_decode_batch(
-        _dev(qkv, "qkv", torch.bfloat16), _dev(k_cache, "k_cache", torch.bfloat16),
-        _dev(v_cache, "v_cache", torch.bfloat16), _dev(pos, "pos", torch.int64), _dev(pos, "pos", torch.int64),
-        _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32), cos.shape[0], _dev(y, "y", torch.bfloat16),
-        ws, cnt, B, k_cache.stride(0), act, n_head, n_query_groups, head_size, rope_n_elem, k_cache.shape[-2],
-        n_splits, float(scale), _stream()))
-    return y
+    return _attention_decode("batch", qkv, (k_cache, v_cache), pos, pos, cos, sin, n_head, n_query_groups, head_size,
+                             rope_n_elem, scale, n_splits, workspace, out, active)
 
 
 def attention_decode_batch_kv8(qkv, cache, pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale,
@@ -846,21 +793,8 @@ def attention_decode_batch_kv8(qkv, cache, pos, cos, sin, n_head, n_query_groups
     """``attention_decode_batch`` over an fp8 cache: ``cache`` is the whole (k codes, v codes, k scales, v scales),
     codes (slots, G, max_seq, 128) uint8 and scales (slots, G, max_seq) fp32. Row b's y, codes and scales are
     bit-identical to ``attention_decode_fused_kv8`` on that row and slot with the same ``n_splits``."""
-    name = "attention_decode_batch_kv8"
-    kc, vc, ks, vs = cache
-    B, y, ws, cnt, act = _batch_args(name, qkv, kc, pos, n_head, n_query_groups, head_size, n_splits, workspace,
-                                     active, out)
-    if kc.shape != vc.shape or kc.shape[-1] != 128 or ks.shape != kc.shape[:3] or vs.shape != ks.shape:
-        raise ValueError(f"{name}: an fp8 batch cache is codes (slots, G, max_seq, 128) uint8 x 2 and scales (slots, "
-                         f"G, max_seq) fp32 x 2, got {tuple(kc.shape)}, {tuple(vc.shape)}, {tuple(ks.shape)}, "
-                         f"{tuple(vs.shape)}")
-    _check(load_library().lga_attention_decode_batch_kv8(
-        _dev(qkv, "qkv", torch.bfloat16), _dev(kc, "k_codes", torch.uint8), _dev(vc, "v_codes", torch.uint8),
-        _dev(ks, "k_scale", torch.float32), _dev(vs, "v_scale", torch.float32), _dev(pos, "pos", torch.int64),
-        _dev(pos, "pos", torch.int64), _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32), cos.shape[0],
-        _dev(y, "y", torch.bfloat16), ws, cnt, B, kc.stride(0), ks.stride(0), act, n_head, n_query_groups, head_size,
-        rope_n_elem, kc.shape[-2], n_splits, float(scale), _stream()))
-    return y
+    return _attention_decode("batch", qkv, tuple(cache), pos, pos, cos, sin, n_head, n_query_groups, head_size,
+                             rope_n_elem, scale, n_splits, workspace, out, active)
 
 
 def spec_accept(logits, window, out=None, token_inout=None, pos_inout=None):

@@ -218,6 +218,42 @@ def test_batch_attention_graph_replay_with_advancing_positions(ops, fp8):
     assert int(ws.counters.abs().sum()) == 0  # re-armed
 
 
+@pytest.mark.parametrize("fp8", [False, True], ids=["bf16", "fp8"])
+def test_window_and_batch_forms_share_one_workspace(ops, fp8):
+    """The model keeps ONE AttentionWorkspace per row count for every decode form (CausalSelfAttention._decode_setup):
+    a window of 2 rows and a batch of 2 sequences, launched in turn through the same workspace, must give the bits they
+    give with a fresh workspace each — every launch leaves the arrival counters as it found them."""
+    H, G, max_seq, n_splits = 4, 2, 64, 4
+    qkv = _qkv(H, G)
+    cos, sin = _rope(max_seq)
+
+    def run(workspace):
+        cache = tuple(t.clone() for t in _cache(2, G, max_seq, fp8))
+        ys = []
+        for i, p in enumerate((38, 40)):
+            rows = qkv[4 * i:4 * i + 2].contiguous()
+            pos0 = torch.tensor([p], device=DEV)
+            slot0 = tuple(t[0] for t in cache)  # views: the window appends to slot 0 of the batch's cache
+            if fp8:
+                ys.append(ops.attention_decode_window_kv8(rows, slot0, pos0, cos, sin, H, G, HS, HS, SCALE, n_splits,
+                                                          workspace=workspace()))
+            else:
+                ys.append(ops.attention_decode_window(rows, slot0[0], slot0[1], pos0, cos, sin, H, G, HS, HS, SCALE,
+                                                      n_splits, workspace=workspace()))
+            ys.append(_batch(ops, qkv[4 * i + 2:4 * i + 4].contiguous(), cache, [p + 2, 43 - p], H, G, n_splits, fp8,
+                             ws=workspace()))
+        return ys, cache
+
+    shared = ops.AttentionWorkspace(2, H, G, HS, n_splits, DEV)
+    got_y, got_cache = run(lambda: shared)
+    ref_y, ref_cache = run(lambda: ops.AttentionWorkspace(2, H, G, HS, n_splits, DEV))
+    assert len(got_y) == 4
+    _same(got_y, ref_y)
+    _same(got_cache, ref_cache)
+    assert not torch.equal(got_cache[0], _cache(2, G, max_seq, fp8)[0])
+    assert int(shared.counters.abs().sum()) == 0  # re-armed by the last launch too
+
+
 def test_batch_attention_argument_errors(ops):
     H, G = 8, 8
     kc, vc = (t.clone() for t in _cache(8, G, S, False))

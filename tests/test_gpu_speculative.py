@@ -242,7 +242,8 @@ def test_new_kernels_use_no_scratch():
     new = {k: v for k, v in scratch.items()
            if "window_append_kernel" in k or "spec_accept_kernel" in k
            or ("attn_kernel" in k and k.split("EEEv")[0].endswith("Lb1ELb1ELb1"))}  # <.., FUSED, PIPE, WINDOW>
-    assert sum("window_append" in k for k in new) == 1 and sum("spec_accept" in k for k in new) == 2
+    # window_append_kernel<KV8>: the bf16 and the fp8 instantiation of the one append kernel
+    assert sum("window_append" in k for k in new) == 2 and sum("spec_accept" in k for k in new) == 2
     assert sum("attn_kernel" in k for k in new) == 5, sorted(new)
     assert all(v == (0, 0) for v in new.values()), new
 

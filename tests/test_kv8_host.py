@@ -248,6 +248,61 @@ def test_kv8_argument_validation_without_gpu():
     assert deq(G=0) != 0 and b"max_seq" in err()
 
 
+_DECODE_SYMBOLS = [f"lga_attention_decode_{form}{kv8}" for form in ("fused", "window", "batch") for kv8 in ("", "_kv8")]
+# (word in lga_last_error_string(), argument overrides, the symbols the case applies to: a substring of the name)
+_DECODE_REFUSALS = [
+    ("null", dict(qkv=None), ""),
+    ("null", dict(y=None), ""),
+    ("null", dict(k_scale=None), "_kv8"),
+    ("geometry", dict(G=3), ""),                    # G does not divide n_head = 8
+    ("128", dict(hs=64, ne=64), ""),
+    ("head_size", dict(hs=64, ne=64), ""),
+    ("128", dict(ne=32), ""),
+    ("q_per_kv", dict(n_head=6), ""),               # 3 heads per group
+    ("empty", dict(S=0), ""),
+    ("empty", dict(rope_rows=0), ""),
+    ("n_splits", dict(splits=0), ""),
+    ("n_splits", dict(splits=257, ws=True), ""),
+    ("workspace", dict(splits=4), ""),
+    ("[1, 8]", dict(rows=0), "window"),
+    ("[1, 8]", dict(rows=9), "window"),
+    ("[1, 8]", dict(rows=0), "batch"),
+    ("[1, 8]", dict(rows=9), "batch"),
+    ("slot_stride", dict(slot_stride=2 * 64 * 128 - 1), "batch"),
+    ("scale_slot_stride", dict(scale_slot_stride=2 * 64 - 1), "batch_kv8"),
+]
+
+
+@pytest.mark.parametrize("symbol,word,over", [(s, w, o) for s in _DECODE_SYMBOLS for w, o, only in _DECODE_REFUSALS
+                                              if only in s])
+def test_decode_attention_entry_points_refuse_before_any_launch(symbol, word, over):
+    """Every lga_attention_decode_* entry point makes the same argument checks, names itself in the message and returns
+    before anything is dereferenced or launched (the pointers are never valid)."""
+    from lit_gpt import ops
+
+    lib = ops.load_library()
+    p = ctypes.c_void_p(256)
+    a = dict(qkv=p, k_scale=p, y=p, ws=False, rows=2, slot_stride=2 * 64 * 128, scale_slot_stride=2 * 64, n_head=8,
+             G=2, hs=128, ne=128, S=64, rope_rows=64, splits=1)
+    assert set(over) <= set(a)
+    a.update(over)
+    ws = p if a["ws"] else None
+    args = [a["qkv"], p, p] + ([a["k_scale"], p] if symbol.endswith("_kv8") else []) + [p]  # qkv, caches, position(s)
+    if "window" not in symbol:
+        args.append(p)  # rope_pos
+    args += [p, p, a["rope_rows"], a["y"], ws, ws]
+    if "fused" not in symbol:
+        args.append(a["rows"])
+    if "batch" in symbol:
+        args += [a["slot_stride"]] + ([a["scale_slot_stride"]] if symbol.endswith("_kv8") else []) + [None]  # active
+    args += [a["n_head"], a["G"], a["hs"], a["ne"], a["S"], a["splits"], 0.1, None]
+    assert len(args) == len(ops.SIGNATURES[symbol])
+    lib.lga_set_error(b"")
+    assert getattr(lib, symbol)(*args) != 0
+    err = lib.lga_last_error_string()
+    assert err.startswith(symbol.encode() + b": ") and word.encode() in err, err
+
+
 def test_ops_wrappers_check_the_cache_layout():
     from lit_gpt import ops
 
