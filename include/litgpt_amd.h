@@ -157,6 +157,22 @@ int lga_int8_gemm(const void* x, const void* xq, const float* sx, const int* col
 int lga_lora_gemv(const void* x, const void* norm_weight, float norm_eps, const void* A, const void* B,
                   const int32_t* row_off, float scaling, const void* base, const void* residual, void* y, int N,
                   int K, int R, int r, lga_stream_t stream);
+/* batched decode, 1 <= M <= 8 rows, each with its own adapter out of a stacked set, in one launch. x (M, K); base
+ * (required, may alias y), residual (or NULL) and y (M, N). A holds n_adapters (R, K) blocks a_stride elements apart,
+ * B n_adapters (N, r) blocks b_stride elements apart (strides: multiples of 8, at least one block); row_off (N) or
+ * NULL and scaling are shared by the set. adapter (M) int32 in DEVICE memory, read by the kernel, so a captured launch
+ * follows a later write of the ids. Contract:
+ *   - row m with adapter[m] = a in [0, n_adapters) has the bits of lga_lora_gemv(x[m], norm_weight, norm_eps,
+ *     A + a * a_stride, B + a * b_stride, row_off, scaling, base[m], residual[m]) (the two kernels run one body);
+ *   - a row whose id is -1, or anything else outside [0, n_adapters), passes through as that kernel's off_n < 0 rows
+ *     do: y = base, then bf16(y + residual) where residual is given. Such a row reads nothing of x, A or B, so a bad
+ *     id cannot read out of bounds;
+ *   - no row's output depends on another row's x or id.
+ * The grid is (lga_lora_gemv's grid, M); the limits on r, R and K are lga_lora_gemv's. */
+int lga_lora_gemv_rows(const void* x, const void* norm_weight, float norm_eps, const void* A, const void* B,
+                       const int32_t* row_off, const int32_t* adapter, int n_adapters, long long a_stride,
+                       long long b_stride, float scaling, const void* base, const void* residual, void* y, int M,
+                       int N, int K, int R, int r, lga_stream_t stream);
 /* prefill, M > 1: t (M, R) bf16 = bf16(x A^T) on the MFMA (x already normed), then the rest of the chain per row over
  * the base output y (M, N) */
 int lga_lora_down(const void* x, const void* A, void* t, int M, int K, int R, lga_stream_t stream);

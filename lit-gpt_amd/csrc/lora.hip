@@ -20,6 +20,11 @@
 // lga_lora_gemv: every workgroup computes ALL R values of t itself (A is small and its re-reads hit L2; a second
 // launch or a grid-wide hand-off would cost more than the R x K dot products), in an order that does not depend on
 // the workgroup, so y does not depend on the grid. Then each thread owns 8 consecutive output rows.
+//
+// lga_lora_gemv_rows (batched decode): up to 8 rows, each with the adapter its device-resident id names out of a
+// stacked set, or none. One more grid dimension over the rows; every workgroup runs the one-row kernel's body on its
+// row (lora_gemv_body), so a row has the one-row launch's bits and depends on no other row. Rows are not grouped by
+// adapter and share no A reads: at M <= 4 with the adapters in L2 the launch is latency-bound either way.
 #include <cstdlib>
 
 #include "decode_ops.h"
@@ -125,10 +130,13 @@ struct LoraGemvArgs {
 
 constexpr int kGemvThreads = 1024, kGemvWaves = kGemvThreads / 64;
 
+// The body of both decode kernels: workgroup blockIdx.x of the one-row launch on the row that ``a`` describes. ``lora``
+// false (lga_lora_gemv_rows only: a row whose adapter id selects none) makes every output row an off_n < 0 row — the
+// norm and the t phase are skipped and nothing of x, A or B is read.
 // RB rows of A per wave and pass: 16 waves x RB rows per pass, the 8 * RB loads of an unrolled step in flight together.
 // The launch is latency-bound (A comes from L2), so what counts is how few dependent rounds of loads a wave makes.
 template <int RB>
-__global__ void __launch_bounds__(kGemvThreads) lora_gemv_kernel(LoraGemvArgs a) {
+__device__ __forceinline__ void lora_gemv_body(const LoraGemvArgs& a, const bool lora) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* xl = (uint4*)smem;  // K/8 uint4: x' in bf16
   __shared__ float t_lds[kLoraMaxR];
@@ -147,14 +155,14 @@ __global__ void __launch_bounds__(kGemvThreads) lora_gemv_kernel(LoraGemvArgs a)
   int off[8];
   if (owner) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) off[i] = up.row_off ? up.row_off[min(n0 + i, up.N - 1)] : 0;
+    for (int i = 0; i < 8; ++i) off[i] = !lora ? -1 : up.row_off ? up.row_off[min(n0 + i, up.N - 1)] : 0;
     if (vec && up.base) base8 = *(const uint4*)(up.base + n0);
     if (vec && up.residual) res8 = *(const uint4*)(up.residual + n0);
   }
 
   // 1. x' into LDS (RMSNorm with lga_rmsnorm's rounding: fp32 sum of squares, bf16(w * (x * rs)))
   float rs = 1.0f;
-  if (a.norm_w) {
+  if (lora && a.norm_w) {
     float ss = 0.0f;
     for (int u = tid; u < n8; u += kGemvThreads) {
       const uint4 v = ((const uint4*)a.x)[u];
@@ -173,7 +181,7 @@ __global__ void __launch_bounds__(kGemvThreads) lora_gemv_kernel(LoraGemvArgs a)
     for (int w = 0; w < kGemvWaves; ++w) tot += red[w];
     rs = 1.0f / sqrtf(tot / (float)a.K + a.eps);
   }
-  for (int u = tid; u < n8; u += kGemvThreads) {
+  for (int u = tid; lora && u < n8; u += kGemvThreads) {
     const uint4 v = ((const uint4*)a.x)[u];
     uint32_t d[4] = {v.x, v.y, v.z, v.w};
     if (a.norm_w) {
@@ -190,7 +198,7 @@ __global__ void __launch_bounds__(kGemvThreads) lora_gemv_kernel(LoraGemvArgs a)
 
   // 2. t: in pass p wave w takes rows (16 p + w) RB .. + RB - 1 of A; lane l the 16-byte chunks l, l + 64, ... of each
   //    row, summed in that order, then one butterfly per row. The same in every workgroup and for every RB.
-  for (int j0 = wave * RB; j0 < R; j0 += kGemvWaves * RB) {
+  for (int j0 = wave * RB; lora && j0 < R; j0 += kGemvWaves * RB) {
     const uint4* ar[RB];
     float s[RB];
 #pragma unroll
@@ -233,7 +241,7 @@ __global__ void __launch_bounds__(kGemvThreads) lora_gemv_kernel(LoraGemvArgs a)
     const uint4* brow = (const uint4*)(up.B + (size_t)n * up.r);
     const float* ts = t_lds + max(off[i], 0);
     float u = 0.0f;
-    for (int c = 0; c < r8; ++c) {
+    for (int c = 0; lora && c < r8; ++c) {
       float b[8];
       unpack8(brow[c], b);
       u = lora_chunk_dot(b, ts + 8 * c, u);
@@ -251,6 +259,36 @@ __global__ void __launch_bounds__(kGemvThreads) lora_gemv_kernel(LoraGemvArgs a)
     for (int i = 0; i < 8; ++i)
       if (n0 + i < up.N) up.y[n0 + i] = f2bf(yv[i]);
   }
+}
+
+template <int RB>
+__global__ void __launch_bounds__(kGemvThreads) lora_gemv_kernel(LoraGemvArgs a) {
+  lora_gemv_body<RB>(a, true);
+}
+
+// ---- batched decode: row m of up to 8 with the adapter adapter[m] of a stacked set, or none -------------------------
+// Grid (the one-row launch's grid, M): workgroup (g, m) is lora_gemv_kernel's workgroup g on row m with adapter
+// adapter[m]'s A and B, through the same body, so row m has that launch's bits. The ids are read from device memory: a
+// captured launch follows them. An id outside [0, n_adapters) selects no adapter and touches neither A nor B.
+struct LoraRowsArgs {
+  const int32_t* adapter;  // [M]
+  int n_adapters;
+  long long a_stride, b_stride;  // elements between the adapters' A (R, K) / B (N, r) blocks
+};
+
+template <int RB>
+__global__ void __launch_bounds__(kGemvThreads) lora_gemv_rows_kernel(LoraGemvArgs a, LoraRowsArgs rw) {
+  const int m = blockIdx.y;
+  const int id = rw.adapter[m];
+  const bool lora = id >= 0 && id < rw.n_adapters;
+  const size_t row = (size_t)m * a.up.N;
+  a.x += (size_t)m * a.K;
+  a.A += lora ? (size_t)id * rw.a_stride : 0;
+  a.up.B += lora ? (size_t)id * rw.b_stride : 0;
+  a.up.base += row;
+  if (a.up.residual) a.up.residual += row;
+  a.up.y += row;
+  lora_gemv_body<RB>(a, lora);
 }
 
 // ---- prefill: t = bf16(X A^T) on the MFMA, then the up-projection over the base output ---------------------------
@@ -410,6 +448,41 @@ extern "C" int lga_lora_gemv(const void* x, const void* norm_weight, float norm_
   if (R <= 16) lga::lora_gemv_kernel<1><<<blocks, lga::kGemvThreads, lds, stream>>>(a);
   else if (R <= 32) lga::lora_gemv_kernel<2><<<blocks, lga::kGemvThreads, lds, stream>>>(a);
   else lga::lora_gemv_kernel<4><<<blocks, lga::kGemvThreads, lds, stream>>>(a);
+  LGA_LAUNCH_RETURN();
+}
+
+extern "C" int lga_lora_gemv_rows(const void* x, const void* norm_weight, float norm_eps, const void* A, const void* B,
+                                  const int32_t* row_off, const int32_t* adapter, int n_adapters, long long a_stride,
+                                  long long b_stride, float scaling, const void* base, const void* residual, void* y,
+                                  int M, int N, int K, int R, int r, hipStream_t stream) {
+  LGA_CHECK_ARG(x && A && B && adapter && base && y, "lga_lora_gemv_rows: null pointer");
+  LGA_CHECK_ARG(M >= 1 && M <= 8, "lga_lora_gemv_rows: M must be in 1..8");
+  LGA_CHECK_ARG(n_adapters >= 1, "lga_lora_gemv_rows: n_adapters must be at least 1");
+  LGA_CHECK_ARG(N > 0 && K > 0 && K % 8 == 0 && K <= 32768,
+                "lga_lora_gemv_rows: K must be a positive multiple of 8, at most 32768");
+  LGA_CHECK_ARG(lga::lora_ranks_ok(R, r),
+                "lga_lora_gemv_rows: needs r % 8 == 0, r <= 64, R % 8 == 0, r <= R <= 192");
+  LGA_CHECK_ARG(a_stride >= (long long)R * K && b_stride >= (long long)N * r && a_stride % 8 == 0 && b_stride % 8 == 0,
+                "lga_lora_gemv_rows: a_stride / b_stride must be multiples of 8 elements of at least one block "
+                "(R * K / N * r)");
+  LGA_CHECK_ARG(((uintptr_t)x | (uintptr_t)A | (uintptr_t)B | (uintptr_t)(norm_weight ? norm_weight : x)) % 16 == 0,
+                "lga_lora_gemv_rows: x, norm_weight, A and B must be 16-B aligned");
+  lga::LoraGemvArgs a;
+  a.x = (const uint16_t*)x;
+  a.norm_w = (const uint16_t*)norm_weight;
+  a.A = (const uint16_t*)A;
+  a.up = lga::LoraUpArgs{nullptr, (const uint16_t*)B, row_off, (const uint16_t*)base, (const uint16_t*)residual,
+                         (uint16_t*)y, 1, N, R, r, scaling};
+  a.K = K;
+  a.eps = norm_eps;
+  a.groups_per_wg = lga::lora_groups_per_wg();
+  const lga::LoraRowsArgs rw{adapter, n_adapters, a_stride, b_stride};
+  const int groups = (N + 7) / 8;
+  const dim3 blocks((groups + a.groups_per_wg - 1) / a.groups_per_wg, M);  // (the one-row launch's grid, M)
+  const size_t lds = (size_t)K * 2;
+  if (R <= 16) lga::lora_gemv_rows_kernel<1><<<blocks, lga::kGemvThreads, lds, stream>>>(a, rw);
+  else if (R <= 32) lga::lora_gemv_rows_kernel<2><<<blocks, lga::kGemvThreads, lds, stream>>>(a, rw);
+  else lga::lora_gemv_rows_kernel<4><<<blocks, lga::kGemvThreads, lds, stream>>>(a, rw);
   LGA_LAUNCH_RETURN();
 }
 

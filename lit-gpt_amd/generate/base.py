@@ -195,6 +195,38 @@ def generate(model: GPT, prompt: torch.Tensor, max_returned_tokens: int, *, temp
 MAX_BATCH = GPT.MAX_BATCH  # sequences per batched decode step (4: lit_gpt/model.py)
 
 
+def _check_adapters(who: str, model: GPT, adapters, n: int):
+    """``adapters`` of a batched call: one entry per prompt, the index of its LoRA adapter in ``model.lora_adapters``
+    (lit_gpt.lora.attach_many) or None. Returns (the set or None, the list); on a model with a set and no ``adapters``
+    every prompt runs without one. Raises before anything is launched."""
+    aset = getattr(model, "lora_adapters", None)
+    if adapters is None:
+        return aset, [None] * n
+    if aset is None:
+        raise ValueError(f"{who}: adapters given, but the model carries no adapter set (lit_gpt.lora.attach_many)")
+    adapters = list(adapters)
+    if len(adapters) != n:
+        raise ValueError(f"{who}: {len(adapters)} adapters for {n} prompts")
+    return aset, [aset.check(a, who) for a in adapters]
+
+
+class _selected:
+    """``with _selected(aset, i)``: one-sequence calls run adapter i of the set (None: the base model); the set's
+    earlier selection returns on exit. Without a set it does nothing."""
+
+    def __init__(self, aset, i) -> None:
+        self.aset, self.i = aset, i
+
+    def __enter__(self):
+        if self.aset is not None:
+            self.before = self.aset.selected
+            self.aset.select(self.i)
+
+    def __exit__(self, *exc) -> None:
+        if self.aset is not None:
+            self.aset.select(self.before)
+
+
 def _batch_steps(dg, n_steps: int, eos_id: Optional[int]):
     """Drive a batched step executor (lit_gpt.runtime.BatchDecodeGraph: ``B``, ``token`` (B,) holding the first
     step's tokens, ``chunk``, ``step()``, ``steps()``) for ``n_steps`` steps in all. Returns the (n_steps, B) token
@@ -231,16 +263,19 @@ def _batch_steps(dg, n_steps: int, eos_id: Optional[int]):
 @torch.inference_mode()
 def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int, *, temperature: float = 1.0,
                    top_k: Optional[int] = None, eos_id: Optional[int] = None, seeds: Optional[List[int]] = None,
-                   use_graph: bool = True, top_p: float = 1.0) -> List[torch.Tensor]:
+                   use_graph: bool = True, top_p: float = 1.0, adapters=None) -> List[torch.Tensor]:
     """Continue up to MAX_BATCH = 4 prompts (each (T_b,), lengths may differ) by ``max_new_tokens`` tokens each,
     decoding them together: every decode step streams the weights once for all sequences (the multi-row GEMVs; attention runs per
     sequence). Sequence b gets exactly the tokens ``generate`` returns for ``prompts[b]`` alone (under sampling: with
     ``SamplerRNG(seed=seeds[b])``). Each prompt is prefilled alone into slot b of the KV cache, which is rebuilt for
     ``len(prompts)`` sequences when it holds fewer. A sequence that meets ``eos_id`` stops collecting tokens; the
-    batch steps on until all have or ``max_new_tokens`` is reached. Returns the (T_b + new_b,) ids per sequence."""
+    batch steps on until all have or ``max_new_tokens`` is reached. Returns the (T_b + new_b,) ids per sequence.
+    ``adapters`` (a ``lit_gpt.lora.attach_many`` model): per prompt the index of its LoRA adapter or None; sequence b
+    then gets the tokens of ``generate`` under ``model.lora_adapters.select(adapters[b])``."""
     B = len(prompts)
     if B == 0:
         raise ValueError("generate_batch: no prompts")
+    aset, adapters = _check_adapters("generate_batch", model, adapters, B)
     if top_p != 1.0:
         _check_model_top_p("generate_batch", model, top_p, temperature, top_k)
         if temperature == 0.0:
@@ -265,15 +300,18 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
     if temperature > 0.0:
         rngs = [SamplerRNG(device, None if seeds is None else seeds[b]) for b in range(B)]
     if B == 1:
-        return [generate(model, prompts[0], prompts[0].size(0) + max_new_tokens, temperature=temperature, top_k=top_k,
-                         eos_id=eos_id, use_graph=use_graph, rng=None if rngs is None else rngs[0], **tp)]
+        with _selected(aset, adapters[0]):
+            return [generate(model, prompts[0], prompts[0].size(0) + max_new_tokens, temperature=temperature,
+                             top_k=top_k, eos_id=eos_id, use_graph=use_graph, rng=None if rngs is None else rngs[0],
+                             **tp)]
     kv = model.transformer.h[0].attn.kv_cache
     if kv is None or kv.k.size(0) < B:
         model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.cache_dtype)
     firsts = []
     for b, prompt in enumerate(prompts):  # the single path's prefill (next_token), on slot b
         T = prompt.size(0)
-        logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=b)
+        with _selected(aset, adapters[b]):
+            logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=b)
         firsts.append(sample(logits, temperature=temperature, top_k=top_k,
                              rng=None if rngs is None else rngs[b], **tp).to(dtype=prompt.dtype).clone())
     n_steps = max_new_tokens - 1
@@ -283,7 +321,8 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
 
     dg = BatchDecodeGraph(model, torch.cat(firsts), [p.size(0) for p in prompts],
                           chunk=DECODE_CHUNK if use_graph and n_steps > DECODE_CHUNK else 1,
-                          temperature=temperature, top_k=top_k, rngs=rngs, use_graph=use_graph, **tp)
+                          temperature=temperature, top_k=top_k, rngs=rngs, use_graph=use_graph,
+                          **({} if aset is None else {"adapters": adapters}), **tp)
     out, lengths = _batch_steps(dg, n_steps, eos_id)
     return [torch.cat([p, f, out[:n_b, b].to(p.dtype)]) for b, (p, f, n_b) in enumerate(zip(prompts, firsts, lengths))]
 
@@ -292,19 +331,22 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
 def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens, *, batch_size: int = MAX_BATCH,
                         temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None,
                         seeds: Optional[List[int]] = None, use_graph: bool = True,
-                        chunk: int = DECODE_CHUNK, top_p: float = 1.0) -> List[torch.Tensor]:
+                        chunk: int = DECODE_CHUNK, top_p: float = 1.0, adapters=None) -> List[torch.Tensor]:
     """Continuous batching: any number of prompts (each (T_i,)) through ``min(batch_size, len(prompts))`` slots of the
     batched decode step. ``max_new_tokens``: an int, or one per prompt. A prompt enters a free slot through the single
     path's prefill; a sequence that met ``eos_id`` or its budget leaves its slot to the next prompt of the queue while
     the other slots keep decoding, their state on the device (lit_gpt.runtime.SlotDecodeGraph; the bookkeeping is
     lit_gpt.scheduler.SlotScheduler). Returns the (T_i + new_i,) ids in prompt order; ``result[i]`` is exactly what
     ``generate(model, prompts[i], T_i + max_new_i, ..., rng=SamplerRNG(device, seeds[i]))`` returns on a cache of the
-    same ``max_seq_length``. Refuses what ``generate_batch`` refuses."""
+    same ``max_seq_length``. Refuses what ``generate_batch`` refuses. ``adapters`` (a ``lit_gpt.lora.attach_many``
+    model): per prompt the index of its LoRA adapter or None; ``result[i]`` is then that ``generate`` under
+    ``model.lora_adapters.select(adapters[i])``, and a slot takes its next sequence's adapter without a recapture."""
     from lit_gpt.scheduler import SlotScheduler
 
     n = len(prompts)
     if n == 0:
         raise ValueError("generate_continuous: no prompts")
+    aset, adapters = _check_adapters("generate_continuous", model, adapters, n)
     if top_p != 1.0:
         _check_model_top_p("generate_continuous", model, top_p, temperature, top_k)
         if temperature == 0.0:
@@ -323,9 +365,12 @@ def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens,
     sched = SlotScheduler([p.size(0) for p in prompts], max_new_tokens, B, chunk=chunk, eos_id=eos_id, seeds=seeds if sampling else None, max_seq_length=model.max_seq_length)
     budgets = [s + 1 for s in sched.steps_budget]
     if B == 1:  # one slot: the single path, one prompt after the other
-        return [generate(model, p, p.size(0) + m, temperature=temperature, top_k=top_k, eos_id=eos_id,
-                         use_graph=use_graph, rng=SamplerRNG(device, seeds[i]) if sampling else None, **tp)
-                for i, (p, m) in enumerate(zip(prompts, budgets))]
+        out = []
+        for i, (p, m) in enumerate(zip(prompts, budgets)):
+            with _selected(aset, adapters[i]):
+                out.append(generate(model, p, p.size(0) + m, temperature=temperature, top_k=top_k, eos_id=eos_id,
+                                    use_graph=use_graph, rng=SamplerRNG(device, seeds[i]) if sampling else None, **tp))
+        return out
     if sampling and not graph_sampling(model, temperature, top_k, **tp):
         raise NotImplementedError("generate_continuous: sampling runs on the device sampler only (temperature > 0 "
                                   f"with top_k in [1, {ops.MAX_TOP_K}] over bf16 logits)")
@@ -345,12 +390,14 @@ def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens,
         while (fill := sched.next_fill()) is not None:  # the single path's prefill (next_token), on the free slot
             b, i = fill
             prompt, T = prompts[i], prompts[i].size(0)
-            logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=b)
+            with _selected(aset, adapters[i]):
+                logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True,
+                               kv_slot=b)
             firsts[i] = sample(logits, temperature=temperature, top_k=top_k,
                                rng=SamplerRNG(device, seeds[i]) if sampling else None,
                                **tp).to(dtype=prompt.dtype).clone()
             if sched.start(b):
-                ex.fill(b, firsts[i], T)
+                ex.fill(b, firsts[i], T, **({} if aset is None else {"adapter": adapters[i]}))
         if sched.done:
             break
         n_steps = sched.next_launch()

@@ -16,6 +16,11 @@ Differences from the reference:
     the generated ids are printed. The model is ``checkpoint_dir`` when that holds ``lit_config.json`` and
     ``lit_model.pth``, else a random-init model of the registered config NAME; the adapter is ``lora_path`` when that
     file exists, else a seeded random one (``lit_gpt.lora.random_adapter``).
+  * ``--lora_paths P0 P1 ... --prompts_file FILE --batch_size B`` serves several adapters on one quantized base
+    (``lit_gpt.lora.attach_many``, ``generate.base.generate_continuous``): each line of FILE is ``INDEX<TAB>instruction``
+    (under ``--synthetic``: ``INDEX<TAB>prompt length``), INDEX a position in ``--lora_paths`` or ``-`` for no adapter.
+    Up to B <= 4 requests decode together, each row of the batched step with its own adapter; the answers are printed
+    in file order. 4-bit bases only, never merged.
 """
 
 from __future__ import annotations
@@ -24,7 +29,7 @@ import argparse
 import sys
 import time
 from pathlib import Path
-from typing import List, Optional
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -32,8 +37,9 @@ wd = Path(__file__).parent.parent.resolve()
 if str(wd) not in sys.path:
     sys.path.append(str(wd))
 
-from generate.base import build_model, generate, top_k_arg  # noqa: E402
-from lit_gpt import lora  # noqa: E402
+from generate.base import MAX_BATCH, build_model, generate, generate_continuous, top_k_arg  # noqa: E402
+from lit_gpt import lora, ops  # noqa: E402
+from lit_gpt import quantize as quantize_mod  # noqa: E402
 
 lora_r = 8
 lora_alpha = 16
@@ -61,6 +67,125 @@ def generate_prompt(example: dict) -> str:
 def _lora_kwargs() -> dict:
     return dict(r=lora_r, alpha=lora_alpha, dropout=lora_dropout, to_query=lora_query, to_key=lora_key,
                 to_value=lora_value, to_projection=lora_projection, to_mlp=lora_mlp, to_head=lora_head)
+
+
+def parse_requests(text: str, n_adapters: int, synthetic: bool = False) -> List[Tuple[Optional[int], object]]:
+    """The requests of a ``--prompts_file``: per non-empty line ``INDEX<TAB>instruction`` (``synthetic``:
+    ``INDEX<TAB>prompt length``) -> (adapter index or None for ``-``, instruction or length). A line without a tab, an
+    INDEX that is no position in ``--lora_paths`` or a prompt length that is no positive integer raises ValueError."""
+    out: List[Tuple[Optional[int], object]] = []
+    for no, line in enumerate(text.splitlines(), 1):
+        if not line.strip():
+            continue
+        index, tab, body = line.partition("\t")
+        if not tab:
+            raise ValueError(f"prompts file line {no}: expected INDEX<TAB>{'prompt length' if synthetic else 'instruction'}")
+        index = index.strip()
+        if index == "-":
+            adapter = None
+        elif index.isdigit() and int(index) < n_adapters:
+            adapter = int(index)
+        else:
+            raise ValueError(f"prompts file line {no}: INDEX {index!r} is neither '-' nor a position in the "
+                             f"{n_adapters} --lora_paths")
+        if synthetic:
+            if not body.strip().isdigit() or int(body) < 1:
+                raise ValueError(f"prompts file line {no}: prompt length {body.strip()!r} is no positive integer")
+            out.append((adapter, int(body)))
+        else:
+            out.append((adapter, body.strip()))
+    if not out:
+        raise ValueError("prompts file: no requests")
+    return out
+
+
+@torch.inference_mode()
+def serve(lora_paths: Sequence[Path], prompts_file: Path, batch_size: int = MAX_BATCH, *,
+          checkpoint_dir: Path = Path("checkpoints/stabilityai/stablelm-base-alpha-3b"),
+          quantize: Optional[str] = None, max_new_tokens: int = 100, top_k: Optional[int] = 200,
+          temperature: float = 0.8, precision: Optional[str] = None, merge: Optional[bool] = None,
+          synthetic: Optional[str] = None, top_p: float = 1.0) -> List[List[int]]:
+    """The requests of ``prompts_file`` (``parse_requests``), each with the adapter of ``lora_paths`` it names, through
+    ``generate_continuous`` on ``batch_size`` slots; returns the token ids per request, in file order. Everything that
+    cannot run is refused before the model is built."""
+    precision = precision or "bf16-true"
+    if precision != "bf16-true":
+        raise NotImplementedError("several adapters in a batch compute in bf16 (bf16-true)")
+    if merge:
+        raise NotImplementedError("--merge with --lora_paths: several adapters share one base and cannot be merged "
+                                  "into it; they run next to the quantized weight")
+    if quantize is None:
+        raise NotImplementedError("--lora_paths with a bf16 base: the batched decode streams 4-bit weights only "
+                                  f"(--quantize {quantize_mod.ROWS_MODES})")
+    fmt, _ = quantize_mod.parse_mode(quantize)
+    if fmt not in (ops.FMT_Q4G, ops.FMT_NF4, ops.FMT_FP4):
+        raise NotImplementedError(f"--lora_paths with --quantize {quantize}: the batched decode streams 4-bit weights "
+                                  f"only ({quantize_mod.ROWS_MODES})")
+    if not 1 <= batch_size <= MAX_BATCH:
+        raise NotImplementedError(f"--batch_size {batch_size}: the batched decode runs 1..{MAX_BATCH} sequences per step")
+    lora_paths = [Path(p) for p in lora_paths]
+    if not lora_paths:
+        raise ValueError("--lora_paths: no adapters")
+    checkpoint_dir = Path(checkpoint_dir)
+    have_checkpoint = (checkpoint_dir / "lit_config.json").is_file() and (checkpoint_dir / "lit_model.pth").is_file()
+    if synthetic is not None and not have_checkpoint:
+        config = lora.Config.from_name(synthetic, **_lora_kwargs())
+        checkpoint_path = None
+    else:
+        from lit_gpt.utils import check_valid_checkpoint_dir
+
+        if synthetic is None:
+            check_valid_checkpoint_dir(checkpoint_dir)
+        config = lora.Config.from_json(checkpoint_dir / "lit_config.json", **_lora_kwargs())
+        checkpoint_path = checkpoint_dir / "lit_model.pth"
+    lora.check_supported(config, precision=precision)
+    requests = parse_requests(Path(prompts_file).read_text(), len(lora_paths), synthetic is not None)
+    if synthetic is None:
+        for p in lora_paths:
+            if not p.is_file():
+                raise FileNotFoundError(f"no adapter checkpoint at {str(p)!r} (the output of finetune/lora.py)")
+    adapters = [a for a, _ in requests]
+
+    device = torch.device("cuda", torch.cuda.current_device())
+    tokenizer = None
+    if synthetic is not None:
+        g = torch.Generator(device="cpu").manual_seed(1234)
+        prompts = [torch.randint(0, config.vocab_size, (n,), generator=g, dtype=torch.int32).to(device)
+                   for _, n in requests]
+    else:
+        from lit_gpt.tokenizer import Tokenizer
+
+        tokenizer = Tokenizer(checkpoint_dir)
+        prompts = [tokenizer.encode(generate_prompt({"instruction": text, "input": ""}), device=device)
+                   for _, text in requests]
+    longest = max(p.size(0) for p in prompts)
+    print(f"Loading model {str(checkpoint_path or synthetic)!r} with {config.__dict__}", file=sys.stderr)
+    t0 = time.perf_counter()
+    model = build_model(config, quantize=quantize, device=device, checkpoint_path=checkpoint_path,
+                        max_seq_length=longest + max_new_tokens, prefill_rows=longest)
+    states = [torch.load(str(p), map_location="cpu", weights_only=True) if p.is_file()
+              else lora.random_adapter(config, seed=1234 + i) for i, p in enumerate(lora_paths)]
+    lora.attach_many(model, states, config)
+    print(f"Time to load the model weights: {time.perf_counter() - t0:.02f} seconds.", file=sys.stderr)
+
+    torch.manual_seed(1234)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ys = generate_continuous(model, prompts, max_new_tokens, batch_size=batch_size, temperature=temperature,
+                             top_k=top_k, eos_id=tokenizer.eos_id if tokenizer is not None else None,
+                             adapters=adapters, **({"top_p": top_p} if top_p < 1.0 else {}))
+    torch.cuda.synchronize()
+    t = time.perf_counter() - t0
+    for y in ys:
+        if tokenizer is not None:
+            print(tokenizer.decode(y).split("### Response:")[1].strip())
+        else:
+            print(y.tolist())
+    tokens_generated = sum(y.size(0) - p.size(0) for y, p in zip(ys, prompts))
+    print(f"\n\nTime for inference: {t:.02f} sec total, {tokens_generated / t:.02f} tokens/sec over "
+          f"{len(prompts)} requests", file=sys.stderr)
+    print(f"Memory used: {torch.cuda.max_memory_allocated() / 1e9:.02f} GB", file=sys.stderr)
+    return [y.tolist() for y in ys]
 
 
 @torch.inference_mode()
@@ -159,7 +284,20 @@ def _cli(argv=None) -> None:
     p.add_argument("--synthetic", default=None, help="no tokenizer: synthetic prompt ids; random-init model of this "
                                                      "registered config name unless checkpoint_dir holds one")
     p.add_argument("--prompt_len", type=int, default=16)
+    p.add_argument("--lora_paths", type=Path, nargs="+", default=None,
+                   help="several adapters on one quantized base, served together (with --prompts_file)")
+    p.add_argument("--prompts_file", type=Path, default=None,
+                   help="one request per line, INDEX<TAB>instruction (--synthetic: INDEX<TAB>prompt length); INDEX is "
+                        "a position in --lora_paths, or - for no adapter")
+    p.add_argument("--batch_size", type=int, default=MAX_BATCH, help="requests decoding together (--lora_paths)")
     a = p.parse_args(argv)
+    if (a.lora_paths is None) != (a.prompts_file is None):
+        p.error("--lora_paths and --prompts_file go together")
+    if a.lora_paths is not None:
+        serve(a.lora_paths, a.prompts_file, a.batch_size, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize,
+              max_new_tokens=a.max_new_tokens, top_k=a.top_k, temperature=a.temperature, precision=a.precision,
+              merge=a.merge, synthetic=a.synthetic, top_p=a.top_p)
+        return
     main(a.prompt, a.input, a.lora_path, a.checkpoint_dir, a.quantize, a.max_new_tokens, a.top_k, a.temperature,
          a.precision, a.merge, a.synthetic, a.prompt_len, a.top_p)
 

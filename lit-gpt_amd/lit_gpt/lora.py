@@ -17,6 +17,12 @@ uses the segment of its slot — ``row_off[n]`` = its first row, -1 where the sl
 ``lora_ind`` / ``zero_pad`` / grouped ``conv1d`` (lora.py:263-278, :281-377) scattered once: reference ``lora_B`` row i
 lands at output row ``lora_ind[i]``. r is zero-padded to a multiple of 8 (exact zeros in the fp32 sums).
 
+``attach_many`` attaches SEVERAL adapters of one ``Config`` to a 4-bit base for batched serving: every targeted Linear
+becomes a ``MultiLoraLinear`` with the adapters stacked (``lora_A`` (n, R, K), ``lora_B`` (n, N, r)), and the model's
+``AdapterSet`` (``model.lora_adapters``) says which adapter runs where — ``select(i)`` for one-sequence calls, device-
+resident row ids for the batched decode step, which applies every row's own adapter in one ``lga_lora_gemv_rows`` per
+adapted Linear (several adapters per batch).
+
 ``dropout`` is accepted and ignored: inference makes it the identity.
 """
 
@@ -186,6 +192,109 @@ class LoraLinear(quantize._Kernels, nn.Module):
         return f"r={self.lora_B.shape[1]}, segments={self.lora_A.shape[0] // self.lora_B.shape[1]}, scaling={self.scaling}"
 
 
+class AdapterSet:
+    """The adapters of one ``attach_many`` model (``model.lora_adapters``) and which of them runs where. ``rows``
+    (ops.MAX_GEMV_ROWS,) int32 on the device, -1 (no adapter) at first: the id of every row of the batched decode step,
+    read by ``lga_lora_gemv_rows`` itself, so a captured step follows ``assign``. ``select`` is the host-side choice of
+    the one-sequence calls (prefill, ``generate``): those run the single-adapter kernels on adapter i's views."""
+
+    def __init__(self, n: int, device) -> None:
+        self.n = int(n)
+        self.rows = torch.full((ops.MAX_GEMV_ROWS,), -1, dtype=torch.int32, device=device)
+        self.selected: Optional[int] = None
+
+    def check(self, i: Optional[int], who: str = "AdapterSet") -> Optional[int]:
+        if i is None:
+            return None
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < self.n:
+            raise ValueError(f"{who}: adapter {i!r} is not None or an index into the set's {self.n} adapters")
+        return i
+
+    def assign(self, b: int, i: Optional[int]) -> None:
+        """Row (slot) b of the batched step runs adapter i from now on, None = no adapter: a stream-ordered device
+        write."""
+        if not 0 <= b < self.rows.numel():
+            raise ValueError(f"AdapterSet.assign: row {b} of {self.rows.numel()}")
+        i = self.check(i, "AdapterSet.assign")
+        self.rows[b:b + 1].fill_(-1 if i is None else i)
+
+    def select(self, i: Optional[int]) -> "AdapterSet":
+        """One-sequence calls run adapter i from now on, None = the plain base model."""
+        self.selected = self.check(i, "AdapterSet.select")
+        return self
+
+
+class MultiLoraLinear(quantize._Kernels, nn.Module):
+    """A base Linear with the n adapters of an ``AdapterSet`` stacked next to it: ``lora_A`` (n, R, K) and ``lora_B``
+    (n, N, r), adapter i of each with the bits ``build_layout`` gives that adapter alone; ``row_off`` and ``scaling``
+    are shared (one ``Config`` for the set). One row or a prefill runs as ``LoraLinear`` does on the views of the
+    set's selected adapter, or as the plain base without one. The batched decode step (``gemv_rows``) runs the base's
+    rows GEMV and ONE ``lga_lora_gemv_rows`` in place, every row with the adapter ``adapters.rows`` names."""
+
+    def __init__(self, base: nn.Module, lora_A: torch.Tensor, lora_B: torch.Tensor, row_off: Optional[torch.Tensor],
+                 scaling: float, adapters: AdapterSet) -> None:
+        super().__init__()
+        k = quantize.kernels(base)
+        if k.act_dtype != torch.bfloat16:
+            raise NotImplementedError("a LoRA adapter on an fp32 Linear (--precision 32-true): the adapter kernels "
+                                      "compute in bf16 (bf16-true)")
+        dev = base.weight.device
+        self.base = base
+        self._kernels = k
+        self.adapters = adapters
+        self.in_features, self.out_features = k.in_features, k.out_features
+        self.register_buffer("lora_A", lora_A.to(device=dev, dtype=torch.bfloat16).contiguous())
+        self.register_buffer("lora_B", lora_B.to(device=dev, dtype=torch.bfloat16).contiguous())
+        self.register_buffer("row_off", None if row_off is None else row_off.to(device=dev, dtype=torch.int32))
+        self.scaling = float(scaling)
+        if self.lora_A.dim() != 3 or self.lora_B.dim() != 3 or not self.lora_A.shape[0] == self.lora_B.shape[0] == adapters.n:
+            raise ValueError(f"stacked adapters lora_A {tuple(self.lora_A.shape)} / lora_B {tuple(self.lora_B.shape)} "
+                             f"for a set of {adapters.n}")
+        ops._lora_dims(self.lora_A[0], self.lora_B[0], self.row_off, "MultiLoraLinear")
+        if self.lora_A.shape[2] != self.in_features or self.lora_B.shape[1] != self.out_features:
+            raise ValueError(f"adapters for ({self.lora_B.shape[1]}, {self.lora_A.shape[2]}) on a Linear of "
+                             f"({self.out_features}, {self.in_features})")
+
+    @property
+    def weight(self) -> torch.Tensor:
+        return self.base.weight
+
+    @property
+    def bias(self) -> Optional[torch.Tensor]:
+        return self.base.bias
+
+    def gemv_fuses_norm(self, dual: bool = False) -> bool:
+        return self._kernels.gemv_fuses_norm(dual)
+
+    def pairs_with(self, o) -> bool:  # as LoraLinear: two Linears + lga_swiglu
+        return False
+
+    def gemv(self, x, res, norm_weight, eps):
+        i = self.adapters.selected
+        if i is None:
+            return self._kernels.gemv(x, res, norm_weight, eps)
+        y = self._kernels.gemv(x, None, norm_weight, eps).view(-1)
+        return ops.lora_gemv(x, self.lora_A[i], self.lora_B[i], self.row_off, self.scaling, base=y, residual=res,
+                             norm_weight=norm_weight, eps=eps, out=y)
+
+    def gemm(self, x, res):
+        i = self.adapters.selected
+        if i is None:
+            return self._kernels.gemm(x, res)
+        y = self._kernels.gemm(x, None)
+        t = ops.lora_down(x, self.lora_A[i])
+        return ops.lora_up(t, self.lora_B[i], self.row_off, self.scaling, base=y, residual=res, out=y)
+
+    def gemv_rows(self, x, res, norm_weight, eps):
+        y = self._kernels.gemv_rows(x, None, norm_weight, eps).view(x.shape[0], self.out_features)
+        return ops.lora_gemv_rows(x, self.lora_A, self.lora_B, self.row_off, self.adapters.rows[:x.shape[0]],
+                                  self.scaling, base=y, residual=res, norm_weight=norm_weight, eps=eps, out=y)
+
+    def extra_repr(self) -> str:
+        n, R, _ = self.lora_A.shape
+        return f"adapters={n}, r={self.lora_B.shape[2]}, segments={R // self.lora_B.shape[2]}, scaling={self.scaling}"
+
+
 def _targets(model, config: Config) -> Dict[str, Tuple[nn.Module, str, Optional[tuple]]]:
     """Reference key prefix -> (parent module, attribute, qkv geometry or None) of every Linear the config adapts."""
     out: Dict[str, Tuple[nn.Module, str, Optional[tuple]]] = {}
@@ -204,6 +313,25 @@ def _targets(model, config: Config) -> Dict[str, Tuple[nn.Module, str, Optional[
     return out
 
 
+def _checked_state(lora_state, targets) -> Dict[str, torch.Tensor]:
+    """The adapter tensors of ``lora_state`` (flat or nested under ``"model"``), whose ``lora_`` keys must be exactly
+    those of ``targets``."""
+    state = lora_state.get("model", lora_state)
+    lora_keys = {k for k in state if "lora_" in k}
+    want = {f"{p}.{ab}" for p in targets for ab in ("lora_A", "lora_B")}
+    if lora_keys != want:
+        missing, surplus = sorted(want - lora_keys), sorted(lora_keys - want)
+        raise KeyError(f"adapter checkpoint does not match the LoRA config: missing {missing[:4]} "
+                       f"({len(missing)} in all), not targeted by the config {surplus[:4]} ({len(surplus)} in all)")
+    return state
+
+
+def _refuse_adapted(model) -> None:
+    for m in model.modules():
+        if isinstance(m, (LoraLinear, MultiLoraLinear)):
+            raise RuntimeError("the model already carries a LoRA adapter")
+
+
 def attach(model, lora_state: Dict[str, torch.Tensor], config: Config):
     """Swap the Linears that ``config`` targets for ``LoraLinear`` carrying the adapter tensors of ``lora_state``: the
     reference's key names (``transformer.h.0.attn.attn.lora_A``, ``...mlp.fc_1.lora_B``, ``lm_head.lora_A``, ...),
@@ -215,17 +343,9 @@ def attach(model, lora_state: Dict[str, torch.Tensor], config: Config):
     dtype = model.transformer.wte.weight.dtype
     check_supported(config, precision="32-true" if dtype == torch.float32 else "bf16-true",
                     world_size=1 if group is None else group.world)
-    state = lora_state.get("model", lora_state)
-    lora_keys = {k for k in state if "lora_" in k}
     targets = _targets(model, config)
-    want = {f"{p}.{ab}" for p in targets for ab in ("lora_A", "lora_B")}
-    if lora_keys != want:
-        missing, surplus = sorted(want - lora_keys), sorted(lora_keys - want)
-        raise KeyError(f"adapter checkpoint does not match the LoRA config: missing {missing[:4]} "
-                       f"({len(missing)} in all), not targeted by the config {surplus[:4]} ({len(surplus)} in all)")
-    for m in model.modules():
-        if isinstance(m, LoraLinear):
-            raise RuntimeError("the model already carries a LoRA adapter")
+    state = _checked_state(lora_state, targets)
+    _refuse_adapted(model)
     new = {}
     for prefix, (parent, name, qkv) in targets.items():  # every layout first: a bad tensor leaves the model as it was
         base = getattr(parent, name)
@@ -238,6 +358,44 @@ def attach(model, lora_state: Dict[str, torch.Tensor], config: Config):
     for parent, name, base, A, B, row_off in new.values():
         setattr(parent, name, LoraLinear(base, A, B, row_off, config.alpha / config.r))
     return model
+
+
+def attach_many(model, lora_states: Sequence[Dict[str, torch.Tensor]], config: Config) -> AdapterSet:
+    """Attach several adapters of ONE ``config`` (same r, alpha and targets) to a model for batched serving: every
+    targeted Linear becomes a ``MultiLoraLinear`` holding the adapters stacked, adapter i in the layout ``attach``
+    gives it alone. Each state is checked as ``attach`` checks its own (a missing, surplus or mis-shaped tensor
+    raises and leaves the model as it was), and an already-adapted model is refused. Returns the ``AdapterSet``, also
+    kept as ``model.lora_adapters``: ``select(i)`` for one-sequence calls, ``assign(b, i)`` for the rows of a batched
+    decode step (generate.base.generate_batch / generate_continuous take ``adapters=[...]``)."""
+    from lit_gpt import comm
+
+    if len(lora_states) == 0:
+        raise ValueError("attach_many: no adapters")
+    group = comm.get_default()
+    dtype = model.transformer.wte.weight.dtype
+    check_supported(config, precision="32-true" if dtype == torch.float32 else "bf16-true",
+                    world_size=1 if group is None else group.world)
+    targets = _targets(model, config)
+    states = [_checked_state(s, targets) for s in lora_states]
+    _refuse_adapted(model)
+    if getattr(model, "lora_adapters", None) is not None:
+        raise RuntimeError("the model already carries a LoRA adapter")
+    adapters = AdapterSet(len(states), model.transformer.wte.weight.device)
+    new = []
+    for prefix, (parent, name, qkv) in targets.items():  # every layout first: a bad tensor leaves the model as it was
+        base = getattr(parent, name)
+        layouts = [build_layout(st[f"{prefix}.lora_A"].detach().float().cpu(),
+                                st[f"{prefix}.lora_B"].detach().float().cpu(), config.r, base.out_features, qkv)
+                   for st in states]
+        if layouts[0][0].shape[1] != base.in_features:
+            raise ValueError(f"{prefix}.lora_A has {layouts[0][0].shape[1]} columns, the Linear {base.in_features} "
+                             "inputs")
+        new.append((parent, name, base, torch.stack([l[0] for l in layouts]), torch.stack([l[1] for l in layouts]),
+                    layouts[0][2]))  # (row_off depends on the config alone)
+    for parent, name, base, A, B, row_off in new:
+        setattr(parent, name, MultiLoraLinear(base, A, B, row_off, config.alpha / config.r, adapters))
+    model.lora_adapters = adapters
+    return adapters
 
 
 def merge_lora_weights(model) -> None:

@@ -145,17 +145,22 @@ class GPT(nn.Module):
         if B > self.MAX_BATCH:
             raise NotImplementedError(f"batch size {B}: the MI355X batched decode runs at most {self.MAX_BATCH} "
                                       "sequences per step")
-        self._rows_check("batch size > 1")
+        self._rows_check("batch size > 1", adapters=True)
 
-    def _rows_check(self, what: str) -> None:
-        """What every multi-row decode step (the batched step, the speculative verify window) needs of the model."""
+    def _rows_check(self, what: str, adapters: bool = False) -> None:
+        """What every multi-row decode step (the batched step, the speculative verify window) needs of the model.
+        ``adapters`` (the batched step only): a ``lora.MultiLoraLinear`` (``lora.attach_many``: one adapter per row of
+        the batch) counts as its base Linear; a single-adapter ``LoraLinear`` stays refused."""
+        from lit_gpt.lora import MultiLoraLinear  # (lit_gpt.lora imports this package)
 
         def four_bit(lin, name):
+            if adapters and isinstance(lin, MultiLoraLinear) and not lin._forward_hooks:
+                lin = lin.base
             if type(lin) is not quantize.QuantLinear or lin._forward_hooks:
                 raise NotImplementedError(
                     f"{what} with {name} a {type(lin).__name__}: the multi-row decode GEMV streams plain "
                     f"4-bit Linears only (--quantize {quantize.ROWS_MODES}); LoRA-attached, bnb.int8, bf16 and fp32 "
-                    "Linears decode one sequence at a time")
+                    "Linears decode one sequence at a time (a batch takes adapters attached with lora.attach_many)")
 
         for i, blk in enumerate(self.transformer.h):
             if blk.config.parallel_residual or not isinstance(blk.norm_1, RMSNorm):

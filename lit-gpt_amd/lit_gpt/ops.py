@@ -61,6 +61,8 @@ SIGNATURES = {
     "lga_int8_quantize_act": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     "lga_int8_gemm": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_lora_gemv": [_P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
+    "lga_lora_gemv_rows": [_P, _P, _F, _P, _P, _P, _P, _I, ctypes.c_longlong, ctypes.c_longlong, _F, _P, _P, _P, _I,
+                           _I, _I, _I, _I, _P],
     "lga_lora_down": [_P, _P, _P, _I, _I, _I, _P],
     "lga_lora_up": [_P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_lora_merge": [_P, _P, _P, _P, _F, _I, _I, _I, _I, _P],
@@ -508,6 +510,35 @@ def lora_gemv(x, A, B, row_off, scaling, *, base=None, residual=None, norm_weigh
                                         _opt(row_off, "row_off", torch.int32), float(scaling),
                                         _opt(base, "base", torch.bfloat16), _opt(residual, "residual", torch.bfloat16),
                                         _dev(y, "y", torch.bfloat16), N, K, R, r, _stream()))
+    return y
+
+
+def lora_gemv_rows(x, A, B, row_off, adapter, scaling, *, base, residual=None, norm_weight=None, eps=1e-5, out=None):
+    """Up to ``MAX_GEMV_ROWS`` rows, each with its own adapter, in one launch (batched decode): x (M, K); A (n, R, K) and
+    B (n, N, r) the stacked adapters; ``adapter`` (M,) int32 on the device, read by the kernel. Row m has the bits of
+    ``lora_gemv(x[m], A[a], B[a], ...)`` for a = adapter[m]; an id outside [0, n) passes ``base`` (+ ``residual``)
+    through. ``base`` (M, N) is required (``out`` may be ``base``)."""
+    if A.dim() != 3 or B.dim() != 3 or A.shape[0] != B.shape[0]:
+        raise ValueError(f"lora_gemv_rows: A {tuple(A.shape)} / B {tuple(B.shape)} must be stacked (n, R, K) / (n, N, r) "
+                         "adapters of one set")
+    n = A.shape[0]
+    N, K, R, r = _lora_dims(A[0], B[0], row_off, "lora_gemv_rows")
+    if x.dim() != 2 or x.shape[1] != K or not 1 <= x.shape[0] <= MAX_GEMV_ROWS:
+        raise ValueError(f"lora_gemv_rows: x {tuple(x.shape)} must be (M, {K}) with 1 <= M <= {MAX_GEMV_ROWS}")
+    M = x.shape[0]
+    if adapter.numel() != M:
+        raise ValueError(f"lora_gemv_rows: adapter holds {adapter.numel()} ids for {M} rows")
+    if base is None:
+        raise ValueError("lora_gemv_rows: base is required")
+    for name, v in (("base", base), ("residual", residual), ("out", out)):
+        if v is not None and v.numel() != M * N:
+            raise ValueError(f"lora_gemv_rows: {name} holds {v.numel()} elements, expected {M} x {N}")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_lora_gemv_rows(
+        _dev(x, "x", torch.bfloat16), _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+        _dev(A, "A", torch.bfloat16), _dev(B, "B", torch.bfloat16), _opt(row_off, "row_off", torch.int32),
+        _dev(adapter, "adapter", torch.int32), n, R * K, N * r, float(scaling), _dev(base, "base", torch.bfloat16),
+        _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16), M, N, K, R, r, _stream()))
     return y
 
 

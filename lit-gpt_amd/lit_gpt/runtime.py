@@ -211,6 +211,19 @@ class WindowDecodeGraph:
         return res[0], res[1:res[0] + 2]
 
 
+def _assign_adapters(model, adapters, B: int) -> None:
+    """Write the adapter ids of the B rows of a batched step (``adapters`` None: no row runs one)."""
+    aset = getattr(model, "lora_adapters", None)
+    if aset is None:
+        if adapters is not None:
+            raise ValueError("adapters given, but the model carries no adapter set (lora.attach_many)")
+        return
+    if adapters is not None and len(adapters) != B:
+        raise ValueError(f"{len(adapters)} adapters for {B} sequences")
+    for b in range(B):
+        aset.assign(b, None if adapters is None else adapters[b])
+
+
 class BatchDecodeGraph:
     """``DecodeGraph`` for B <= GPT.MAX_BATCH (4) sequences that decode in lock step (generate.base.generate_batch):
     one graph per step over device-resident ``token`` (B,), ``pos`` (B,) and ``x_emb`` (B, C). The step is the batched forward
@@ -221,11 +234,15 @@ class BatchDecodeGraph:
     ``chunk`` steps as one graph whose tokens land in ``history`` (chunk, B)."""
 
     def __init__(self, model, first_tokens: torch.Tensor, first_pos, chunk: int = 1, *, temperature: float = 0.0,
-                 top_k: Optional[int] = None, rngs=None, use_graph: bool = True, top_p: float = 1.0) -> None:
+                 top_k: Optional[int] = None, rngs=None, use_graph: bool = True, top_p: float = 1.0,
+                 adapters=None) -> None:
         """``first_tokens`` (B,): each sequence's newest token; ``first_pos``: its position per sequence. Runs one
-        real step eagerly, then captures. ``use_graph=False`` keeps every step eager (tests A/B the two)."""
+        real step eagerly, then captures. ``use_graph=False`` keeps every step eager (tests A/B the two).
+        ``adapters``: per sequence the index of its LoRA adapter in ``model.lora_adapters`` (lora.attach_many) or None,
+        written to the set's device-resident row ids before the first step."""
         dev = first_tokens.device
         B = first_tokens.numel()
+        _assign_adapters(model, adapters, B)
         self.model, self.B = model, B
         self.temperature, self.top_k, self.rngs, self.top_p = float(temperature), top_k, rngs, float(top_p)
         if self.temperature > 0.0 and (rngs is None or len(rngs) != B
@@ -323,9 +340,17 @@ class SlotDecodeGraph:
         self.chunk_graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured = False
 
-    def fill(self, b: int, token: torch.Tensor, pos: int) -> None:
+    def fill(self, b: int, token: torch.Tensor, pos: int, adapter: Optional[int] = None) -> None:
         """Sequence enters slot b: its newest token (a one-element device tensor) at position ``pos``. Stream-ordered
-        device writes; the captured graphs read the same buffers."""
+        device writes; the captured graphs read the same buffers. ``adapter``: on a ``lora.attach_many`` model the
+        index of the sequence's adapter or None, written to the set's row ids (``release`` leaves it: the idle row
+        keeps computing finite values nobody reads)."""
+        aset = getattr(self.model, "lora_adapters", None)
+        if aset is not None:
+            aset.assign(b, adapter)
+        elif adapter is not None:
+            raise ValueError("SlotDecodeGraph.fill: adapter given, but the model carries no adapter set "
+                             "(lora.attach_many)")
         self.token[b:b + 1].copy_(token.reshape(1))
         self.pos[b:b + 1].fill_(int(pos))
         ops.embedding(self.token[b:b + 1], self.model.transformer.wte.weight, out=self.x_emb[b:b + 1])

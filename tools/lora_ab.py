@@ -12,7 +12,16 @@ Method (as tools/int8_ab.py): every kind runs as one captured graph of back-to-b
 (about 1 GB per graph, so no launch finds its weights in the 256 MB last-level cache); the kinds alternate inside each
 of ROUNDS rounds, timed with device events; reported per Linear: median over the rounds, and the minimum.
 
+``--rows`` (several adapters per batch, profiles/lora_rows_ab.txt) replaces the above by two measurements. Per launch:
+one lga_lora_gemv_rows at M = 1, 2, 4 rows (every row another adapter of a stacked set of four) against the M one-row
+lga_lora_gemv launches it replaces, by the same method: graphs of 32 back-to-back launches over distinct adapter sets
+(one per layer of the model, all L2-resident as in a decode step), the kinds alternating. End to end: the synthetic
+Llama-2-7B in int4-g128, four 512-token prompts with four different rank-8 q + v adapters, 256 new tokens each —
+generate_batch at B = 4 against the same four requests served one after another on the single path (select(i) +
+generate), interleaved over three repetitions, and the adapter-free B = 4 rate of the same session.
+
 usage: python tools/lora_ab.py [--rounds 7] [--groups 32,64,128,256] [--no-prefill] [--no-model]
+       python tools/lora_ab.py --rows [--rounds 7] [--no-model]
 """
 import argparse
 import os
@@ -192,12 +201,106 @@ def model(dev, steps=256):
           f"{statistics.median(adapted):.1f} ({ms[1]:.3f} ms/step): +{(ms[1] - ms[0]) * 1e3 / n:.2f} us per adapted Linear")
 
 
+def rows_launch(rounds, dev, layers=32, n_adapters=4):
+    print("several adapters per batch, us per launch site: median (min) over %d alternating rounds | rows - M x one-row"
+          % rounds)
+    print(f"{'shape':12s} {'N x K':>14s} {'M':>2s} {'M x lora_gemv':>17s} {'lora_gemv_rows':>17s}")
+    for name in ("qkv r8", "mlp.proj r8"):
+        N, K, r, segs, fusion = SHAPES[name]
+        nw = torch.ones(K, device=dev).bfloat16()
+        sets = []
+        for _ in range(layers):
+            parts = [adapter(N, K, r, segs, dev) for _ in range(n_adapters)]
+            sets.append((torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts]), parts[0][2]))
+        scaling = 16.0 / r
+        for M in (1, 2, 4):
+            x = torch.randn(M, K, device=dev).bfloat16()
+            res = torch.randn(M, N, device=dev).bfloat16()
+            y = torch.randn(M, N, device=dev).bfloat16()
+            ids = torch.arange(M, device=dev, dtype=torch.int32)
+            fused = {"norm_weight": nw} if fusion == "norm" else {"residual": res}
+
+            def one_row():
+                for A, B, off in sets:
+                    for m in range(M):
+                        kw = {"norm_weight": nw} if fusion == "norm" else {"residual": res[m]}
+                        ops.lora_gemv(x[m], A[m], B[m], off, scaling, base=y[m], out=y[m], **kw)
+
+            def rows():
+                for A, B, off in sets:
+                    ops.lora_gemv_rows(x, A, B, off, ids, scaling, base=y, out=y, **fused)
+
+            graphs = {"one-row": capture(one_row), "rows": capture(rows)}
+            t = {k: [] for k in graphs}
+            for _ in range(rounds):
+                for k, g in graphs.items():
+                    t[k].append(timed(g) / layers)
+            report(f"{name:12s} {N:>7d}x{K:<6d} {M:>2d}", t, layers, ["one-row", "rows"])
+            spread = {k: (max(v) - min(v)) for k, v in t.items()}
+            print(f"{'':32s}run-to-run spread (max - min): one-row {spread['one-row']:.2f}, rows {spread['rows']:.2f}")
+        del sets
+        torch.cuda.empty_cache()
+
+
+@torch.inference_mode()
+def rows_model(dev, T=512, new=256, reps=3):
+    from generate.base import build_model, generate, generate_batch
+    from lit_gpt import lora
+
+    cfg = lora.Config.from_name("Llama-2-7b-hf", r=8, alpha=16, to_query=True, to_value=True)
+    m = build_model(cfg, quantize="int4-g128", device=dev, max_seq_length=T + new)
+    g = torch.Generator().manual_seed(7)
+    prompts = [torch.randint(0, cfg.vocab_size, (T,), generator=g, dtype=torch.int32).to(dev) for _ in range(4)]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def batch(adapters, n):
+        m.set_kv_cache(batch_size=4, device=dev)
+        generate_batch(m, prompts, n, temperature=0.0, **({} if adapters is None else {"adapters": adapters}))
+
+    def sequential(n):
+        m.set_kv_cache(batch_size=1, device=dev)
+        for i, p in enumerate(prompts):
+            m.lora_adapters.select(i)
+            generate(m, p, T + n, temperature=0.0)
+        m.lora_adapters.select(None)
+
+    def decode_rate(fn):  # decode tokens/s: the call's time beyond the same call stopped after the prefill's token
+        return 4 * (new - 1) / (wall(lambda: fn(new)) - wall(lambda: fn(1)))
+
+    batch(None, 8)  # warm-up
+    plain = [decode_rate(lambda n: batch(None, n)) for _ in range(reps)]
+    lora.attach_many(m, [lora.random_adapter(cfg, seed=1234 + i) for i in range(4)], cfg)
+    batch([0, 1, 2, 3], 8)
+    sequential(8)
+    rates = {"batch": [], "sequential": [], "batch, no row adapted": []}
+    for _ in range(reps):
+        rates["batch"].append(decode_rate(lambda n: batch([0, 1, 2, 3], n)))
+        rates["sequential"].append(decode_rate(sequential))
+        rates["batch, no row adapted"].append(decode_rate(lambda n: batch([None] * 4, n)))
+    print(f"Llama-2-7B int4-g128, 4 x {T}-token prompts, {new} new tokens each, four rank-8 q + v adapters; aggregate "
+          f"decode tokens/s, {reps} interleaved repetitions: median (min .. max)")
+    rows = [("adapter-free model, generate_batch B = 4", plain),
+            ("four adapters, generate_batch B = 4", rates["batch"]),
+            ("four adapters, one after another (select + generate)", rates["sequential"]),
+            ("adapter set attached, B = 4, every row without adapter", rates["batch, no row adapted"])]
+    for title, v in rows:
+        print(f"  {title:56s} {statistics.median(v):8.1f} ({min(v):.1f} .. {max(v):.1f})")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--groups", default="0", help="comma-separated LGA_LORA_GROUPS values to sweep (0: the heuristic)")
     ap.add_argument("--no-prefill", action="store_true")
     ap.add_argument("--no-model", action="store_true")
+    ap.add_argument("--rows", action="store_true", help="several adapters per batch: lga_lora_gemv_rows against M "
+                                                        "one-row launches, and generate_batch against sequential service")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("lora_ab.py measures on the GPU; no device found")
@@ -205,6 +308,11 @@ if __name__ == "__main__":
     torch.manual_seed(0)
     ops.load_library()
     print(torch.cuda.get_device_name(0))
+    if a.rows:
+        rows_launch(a.rounds, dev)
+        if not a.no_model:
+            rows_model(dev)
+        sys.exit(0)
     decode(a.rounds, dev, [int(g) for g in a.groups.split(",")])
     if not a.no_prefill:
         prefill(a.rounds, dev)
