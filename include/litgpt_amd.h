@@ -284,6 +284,23 @@ int lga_attention_decode_batch_kv8(const void* qkv, void* k_codes, void* v_codes
                                    int B, long long slot_stride, long long scale_slot_stride, const int32_t* active,
                                    int n_head, int n_query_groups, int head_size, int rope_n_elem, int max_seq,
                                    int n_splits, float scale, lga_stream_t stream);
+/* -- shared-prompt decode attention (n samples of one prompt) ------------------------------------------------------
+ * The batch form for B (1..8) rows that advance in lock step behind ONE prompt whose K / V only slot 0 holds. qkv
+ * (B, (H + 2G) hs); k_cache / v_cache the whole (slots, G, max_seq, hs) bf16 tensors, slot_stride as above. pos (1)
+ * int64 on the device: every row sits at p = pos[0], its cache and its rope position. prefix_len (1) int64 on the
+ * device: P, used as min(max(P, 0), p). Row b scores keys j < P from slot 0 and keys P <= j < p from slot b, scores its
+ * own new key from registers and appends it at row p of slot b. y[b] and row p of slot b have the bits that
+ * lga_attention_decode_batch gives, with the same n_splits, on caches whose slot b holds slot 0's rows [0, P); rows
+ * [0, P) of slots 1..B-1 are never read or written. Both values are read by the kernel, so a captured graph stays
+ * valid as p advances and from prompt to prompt. p at or past max_seq: nothing is stored, keys 0..max_seq-1 are
+ * attended. active (B) int32 may be null; a row with active[b] == 0 is idle (y[b] = 0, slot b bit-unchanged), and an
+ * idle row 0 does not keep the others from reading slot 0. workspace, counters, n_splits and the geometry limits are
+ * the batch form's (one workspace serves both). There is no fp8 form. */
+int lga_attention_decode_shared(const void* qkv, void* k_cache, void* v_cache, const int64_t* pos,
+                                const int64_t* prefix_len, const float* cos, const float* sin, int rope_rows, void* y,
+                                float* workspace, unsigned* counters, int B, long long slot_stride,
+                                const int32_t* active, int n_head, int n_query_groups, int head_size, int rope_n_elem,
+                                int max_seq, int n_splits, float scale, lga_stream_t stream);
 /* lga_rope_kv_append for fp8 caches (T rows): roped q to q_out (T, H, hs); k (roped) and v quantized into the codes
  * and scales at row cache_pos[t] — the bits the decode forms store for the same qkv row. */
 int lga_kv8_rope_append(const void* qkv, void* q_out, void* k_codes, void* v_codes, float* k_scale, float* v_scale,

@@ -509,6 +509,365 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel_kv8(const uint16_t* __res
                                                                active);
 }
 
+// SHARED (n samples of one prompt, lga_attention_decode_shared): the BATCH form for B rows that sit at ONE position p
+// = pos[0] and share the keys j < P = min(max(prefix_len[0], 0), p), which only slot 0 holds. grid.z = a set of R
+// rows; the workgroup carries R x QPK independent (m, l, o) states, one per (row, head) pair, and every pair runs the
+// op sequence of its T = 1 FUSED workgroup: the split bounds of p (one for all rows), the same key -> row group ->
+// step assignment and masks, steps in ascending order, the row's own new key last from registers, the same row-group /
+// wave merges, publish and combine with workspace and counters indexed by t = b. What differs is who loads: a step
+// whose UNR x RG keys all lie below P is loaded ONCE from slot 0 and consumed by every pair; a step that straddles or
+// lies past P is taken per row, keys < P from slot 0 and keys >= P from slot b (the same values as a slot b that held
+// the prefix, so the same bits). All steps of the workgroup, shared ones first, then (row, step) in row order, form one
+// pipelined item sequence: item n sits in ka / va (n even) or kb / vb (n odd) and item n + 1's loads are issued
+// ahead of item n's math, across the change of row too. No state passes between workgroups. Idle rows (active[b] ==
+// 0, or b >= B in the last set) are skipped; a set with no active row returns as the batch form's idle row does.
+// Every multiply-add below is written as the ONE form hipcc gives attn_body in all its fused instantiations (fma, or
+// mul_rn / add_rn; read off their ISA). Left to -ffp-contract, this body's other shape had two of them fused
+// differently (the wave merge's l, the block merge's bl): one ulp apart, one output element in thousands.
+// attn_body's own forms stay the compiler's choice: a hipcc that fuses attn_body differently parts the two kernels, and
+// only the bit-identity tests on the GPU (tests/test_gpu_shared_attention.py) show it; the forms here then follow
+// attn_body's new ISA (or attn_body's merges get written out the same way).
+template <int HS, int QPK, int UNR, int NW, int R>
+__global__ void __launch_bounds__(NW * 64)
+    attn_shared_kernel(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
+                       const int64_t* __restrict__ pos, const int64_t* __restrict__ prefix_len,
+                       uint16_t* __restrict__ y, float* __restrict__ ws, unsigned* __restrict__ cnt, int n_head,
+                       int max_seq, float scale, const float* __restrict__ cos, const float* __restrict__ sin,
+                       int rope_rows, int hsplit, long slot_stride, const int* __restrict__ active, int B) {
+  constexpr int LPR = HS / 8;
+  constexpr int RGW = 64 / LPR;
+  constexpr int RG = NW * RGW;
+  constexpr int NT = NW * 64;
+  constexpr int NP = R * QPK;  // pairs
+  const int split = blockIdx.x, gy = blockIdx.y, b0 = blockIdx.z * R;
+  const int g = gy / hsplit, hsi = gy % hsplit, QPKT = QPK * hsplit;
+  const int n_splits = gridDim.x;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int rg = wave * RGW + lane / LPR;
+  const int sub = lane % LPR;
+  const long p = pos[0];
+  const long pfx = min(max(prefix_len[0], 0L), p);
+  const size_t qkv_row = (size_t)(n_head + 2 * (gridDim.y / hsplit)) * HS;
+  unsigned am = 0;  // the active rows of this set, bit r = row b0 + r
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int b = b0 + r;
+    if (b >= B) continue;
+    if (active == nullptr || active[b] != 0) {
+      am |= 1u << r;
+    } else {  // idle row: zero y[b] (split 0), touch nothing else
+      constexpr int NQ0 = QPK * HS / 4;
+      if (split == 0 && threadIdx.x < NQ0)
+        *(uint2*)(y + ((size_t)b * n_head + (size_t)g * QPKT + hsi * QPK) * HS + threadIdx.x * 4) = make_uint2(0u, 0u);
+    }
+  }
+  if (am == 0) return;
+  const int L = (int)min(p + 1, (long)max_seq);  // keys 0..p (never past the cache)
+  const int chunk = (L + n_splits - 1) / n_splits;
+  const int k_lo = split * chunk;
+  const int k_hi = min(k_lo + chunk, L);
+  const bool owns_new = p < max_seq && k_lo <= p && p < k_hi;
+  const int k_end = min(k_hi, (int)min(p, (long)max_seq));  // key p is scored from registers below
+  const int P = (int)min(pfx, (long)max_seq);               // (keys at or past max_seq are never loaded)
+  const long rp = min(max(p, 0L), (long)rope_rows - 1);
+  const float* cr = cos + (size_t)rp * HS + sub * 8;
+  const float* sr = sin + (size_t)rp * HS + sub * 8;
+  const uint16_t* kbase = kc + (size_t)g * max_seq * HS + sub * 8;  // slot 0
+  const uint16_t* vbase = vc + (size_t)g * max_seq * HS + sub * 8;
+  // one item's loads: key j comes from slot 0 below P, else from the slot `own` elements on (a shared step passes 0);
+  // clamped duplicate rows (past k_end) are masked in consume() and hit in cache
+  auto fetch = [&](kv_regs<false> (&kv)[UNR], kv_regs<false> (&vv)[UNR], int j0, size_t own) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const int j = max(min(j0 + u * RG, k_end - 1), 0);
+      const size_t at = (j < P ? (size_t)0 : own) + (size_t)j * HS;
+      kv[u].d = ld_kv(kbase + at);
+      vv[u].d = ld_kv(vbase + at);
+    }
+  };
+  const int j_first = k_lo + rg;
+
+  uint4 qraw[R][QPK];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int h = 0; h < QPK; ++h) {
+      qraw[r][h] = make_uint4(0u, 0u, 0u, 0u);
+      if (am >> r & 1)
+        qraw[r][h] = *(const uint4*)(q + (size_t)(b0 + r) * qkv_row + ((size_t)g * (QPKT + 2) + hsi * QPK + h) * HS +
+                                     sub * 8);
+    }
+  float cs[8], sn[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    cs[i] = cr[i];
+    sn[i] = sr[i];
+  }
+  uint4 qp[R][QPK];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int h = 0; h < QPK; ++h) qp[r][h] = rope8(qraw[r][h], cs, sn, sub);
+  const float sl2 = scale * 1.4426950408889634f;
+  auto dot8 = [](const uint4 a, const uint4 b) {
+    typedef short s2 __attribute__((ext_vector_type(2)));
+    float d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.x), __builtin_bit_cast(s2, b.x), 0.0f, false);
+    d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.y), __builtin_bit_cast(s2, b.y), d, false);
+    d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.z), __builtin_bit_cast(s2, b.z), d, false);
+    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.w), __builtin_bit_cast(s2, b.w), d, false);
+  };
+  // the item sequence: ns shared steps, then the nown own steps of every active row
+  const int stp = RG * UNR;
+  const int nst = k_end > k_lo ? (k_end - k_lo + stp - 1) / stp : 0;
+  const int ns = min(max(P - k_lo, 0) / stp, nst);  // steps i with k_lo + (i + 1) stp <= P
+  const int nown = nst - ns;
+  const int r_first = __builtin_ctz(am);
+  auto own_of = [&](int r) { return (size_t)(b0 + r) * (size_t)slot_stride; };
+  __builtin_amdgcn_sched_barrier(0);
+  kv_regs<false> ka[UNR], va[UNR], kb[UNR], vb[UNR];
+  if (ns > 0) fetch(ka, va, j_first, 0);
+  else if (nown > 0) fetch(ka, va, j_first, own_of(r_first));
+  constexpr float kMFloor = -1e30f;
+  float m[R][QPK], l[R][QPK], o[R][QPK][8];
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int h = 0; h < QPK; ++h) {
+      m[r][h] = kMFloor;
+      l[r][h] = 0.0f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[r][h][i] = 0.0f;
+    }
+  // one step of one row: attn_body's consume() on that row's QPK states
+  auto consume = [&](float (&mr)[QPK], float (&lr)[QPK], float (&orr)[QPK][8], const uint4 (&qr)[QPK],
+                     const kv_regs<false> (&kv)[UNR], const kv_regs<false> (&vv)[UNR], int j0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int h = 0; h < QPK; ++h) {
+      float s[UNR];
+      float mx = mr[h];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const float sd = mul_rn(row_group_sum<LPR>(dot8(qr[h], kv[u].d)), sl2);
+        s[u] = (j0 + u * RG < k_end) ? sd : -INFINITY;
+        mx = fmaxf(mx, s[u]);
+      }
+      const float c = __builtin_amdgcn_exp2f(mr[h] - mx);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) orr[h][i] = mul_rn(orr[h][i], c);
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const float e = __builtin_amdgcn_exp2f(s[u] - mx);
+        lr[h] = u == 0 ? __builtin_fmaf(lr[h], c, e) : add_rn(lr[h], e);
+        float vf[8];
+        unpack8(vv[u].d, vf);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) orr[h][i] = __builtin_fmaf(e, vf[i], orr[h][i]);
+      }
+      mr[h] = mx;
+    }
+  };
+  int n = 0;  // items consumed so far
+  // item n: issue the next item's loads (if any) into the other buffer, then the math `use` on item n's
+  auto item = [&](bool has_next, int j0_next, size_t own_next, auto&& use) __attribute__((always_inline)) {
+    if (n & 1) {
+      if (has_next) fetch(ka, va, j0_next, own_next);
+      use(kb, vb);
+    } else {
+      if (has_next) fetch(kb, vb, j0_next, own_next);
+      use(ka, va);
+    }
+    ++n;
+  };
+  for (int i = 0; i < ns; ++i) {
+    const bool more = i + 1 < ns;
+    const int j0 = j_first + i * stp;
+    item(more || nown > 0, j0 + stp, more ? (size_t)0 : own_of(r_first),
+         [&](const kv_regs<false>(&kv)[UNR], const kv_regs<false>(&vv)[UNR]) __attribute__((always_inline)) {
+#pragma unroll
+           for (int r = 0; r < R; ++r)
+             if (am >> r & 1) consume(m[r], l[r], o[r], qp[r], kv, vv, j0);
+         });
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (!(am >> r & 1)) continue;
+    const unsigned rest = r + 1 < R ? am >> (r + 1) : 0u;
+    const int r_next = rest ? r + 1 + __builtin_ctz(rest) : -1;
+    for (int i = ns; i < nst; ++i) {
+      const bool more = i + 1 < nst;
+      const int j0 = j_first + i * stp;
+      item(more || r_next >= 0, j_first + (more ? i + 1 : ns) * stp, own_of(more ? r : max(r_next, 0)),
+           [&](const kv_regs<false>(&kv)[UNR], const kv_regs<false>(&vv)[UNR]) __attribute__((always_inline)) {
+             consume(m[r], l[r], o[r], qp[r], kv, vv, j0);
+           });
+    }
+  }
+  if (owns_new && rg == 0) {  // every row's new key/value: rope k, append both to slot b, score from registers
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!(am >> r & 1)) continue;
+      const uint16_t* kvrow = q + (size_t)(b0 + r) * qkv_row + ((size_t)g * (QPKT + 2) + QPKT) * HS + sub * 8;
+      const uint4 kr = rope8(*(const uint4*)kvrow, cs, sn, sub);
+      const uint4 vr = *(const uint4*)(kvrow + HS);
+      if (hsi == 0) {  // one head slice appends; the others score the same key from their registers
+        *(uint4*)(kc + own_of(r) + ((size_t)g * max_seq + p) * HS + sub * 8) = kr;
+        *(uint4*)(vc + own_of(r) + ((size_t)g * max_seq + p) * HS + sub * 8) = vr;
+      }
+      float vf[8];
+      unpack8(vr, vf);
+#pragma unroll
+      for (int h = 0; h < QPK; ++h) {
+        const float sd = row_group_sum<LPR>(dot8(qp[r][h], kr));
+        const float mx = fmaxf(m[r][h], mul_rn(sd, sl2));
+        const float c = __builtin_amdgcn_exp2f(m[r][h] - mx);
+        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(sd, sl2, -mx));
+        l[r][h] = __builtin_fmaf(l[r][h], c, e);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[r][h][i] = __builtin_fmaf(e, vf[i], mul_rn(o[r][h][i], c));
+        m[r][h] = mx;
+      }
+    }
+  }
+  // merge the RGW row groups of this wave, pair by pair
+#pragma unroll
+  for (int off = LPR; off < 64; off <<= 1) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!(am >> r & 1)) continue;
+#pragma unroll
+      for (int h = 0; h < QPK; ++h) {
+        const float mo = __shfl_xor(m[r][h], off), lo = __shfl_xor(l[r][h], off);
+        const float mn = fmaxf(m[r][h], mo);
+        const float ca = __builtin_amdgcn_exp2f(m[r][h] - mn);
+        const float cb = __builtin_amdgcn_exp2f(mo - mn);
+        l[r][h] = __builtin_fmaf(l[r][h], ca, mul_rn(lo, cb));
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          o[r][h][i] = __builtin_fmaf(o[r][h][i], ca, mul_rn(__shfl_xor(o[r][h][i], off), cb));
+        m[r][h] = mn;
+      }
+    }
+  }
+  __shared__ float sm[NW][NP], sl[NW][NP];
+  __shared__ __attribute__((aligned(16))) float so[NW][NP][HS];
+  __shared__ unsigned s_ticket[R];
+  if (lane < LPR) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (!(am >> r & 1)) continue;
+#pragma unroll
+      for (int h = 0; h < QPK; ++h) {
+        if (lane == 0) {
+          sm[wave][r * QPK + h] = m[r][h];
+          sl[wave][r * QPK + h] = l[r][h];
+        }
+        *(float4*)&so[wave][r * QPK + h][sub * 8] = make_float4(o[r][h][0], o[r][h][1], o[r][h][2], o[r][h][3]);
+        *(float4*)&so[wave][r * QPK + h][sub * 8 + 4] = make_float4(o[r][h][4], o[r][h][5], o[r][h][6], o[r][h][7]);
+      }
+    }
+  }
+  __syncthreads();
+  // block merge per row: a thread owns 4 consecutive output columns of one head of the slice, as in attn_body
+  constexpr int NQ = QPK * HS / 4;
+  static_assert(NQ <= NT, "one 4-column item per thread and row");
+  constexpr bool SOLO = LGA_ATTN_SOLO && NQ <= 64;
+  if (SOLO && wave != 0) return;  // (every item sits in wave 0)
+  const bool has_item = threadIdx.x < NQ;
+  const int hq = threadIdx.x / (HS / 4), dq = threadIdx.x % (HS / 4);
+  const size_t slice0 = (size_t)g * QPKT + hsi * QPK;  // first head of this slice
+  auto ws_rsrc = [&](int r) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(ws + ((size_t)(b0 + r) * n_head + slice0) * n_splits * (HS + 4)),
+                                             (short)0, QPK * n_splits * (HS + 4) * 4, 0x00020000);
+  };
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (!(am >> r & 1)) continue;
+    float bm = -INFINITY, bl = 0.0f, bo[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (has_item) {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) bm = fmaxf(bm, sm[w][r * QPK + hq]);
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        const float c = __builtin_amdgcn_exp2f(sm[w][r * QPK + hq] - bm);
+        bl = add_rn(bl, mul_rn(sl[w][r * QPK + hq], c));
+        const float4 ov = *(const float4*)&so[w][r * QPK + hq][dq * 4];
+        bo[0] = __builtin_fmaf(ov.x, c, bo[0]);
+        bo[1] = __builtin_fmaf(ov.y, c, bo[1]);
+        bo[2] = __builtin_fmaf(ov.z, c, bo[2]);
+        bo[3] = __builtin_fmaf(ov.w, c, bo[3]);
+      }
+      if (n_splits == 1) {
+        uint16_t* yr = y + ((size_t)(b0 + r) * n_head + slice0 + hq) * HS + dq * 4;
+        *(uint2*)yr = make_uint2(pack2(bo[0] / bl, bo[1] / bl), pack2(bo[2] / bl, bo[3] / bl));
+      } else {  // publish (m, l, o) of this (row, split): attn_body's layout, row t = b
+        const __amdgpu_buffer_rsrc_t wrs = ws_rsrc(r);
+        const unsigned off = (unsigned)((hq * n_splits + split) * (HS + 4)) * 4;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, make_float4(bo[0], bo[1], bo[2], bo[3])),
+                                               wrs, off + 16 + dq * 16, 0, 16);
+        if (dq == 0)
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, make_float4(bm, bl, 0.0f, 0.0f)), wrs,
+                                                 off, 0, 16);
+      }
+    }
+  }
+  if (n_splits == 1) return;
+  // one drain for all rows' partials, then the rows' arrival counters side by side (thread r counts for row r): the
+  // last-arriving split of a (row, group) combines that row
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  auto ctr_of = [&](int r) { return cnt + ((size_t)(b0 + r) * gridDim.y + gy) * kCounterStride; };
+  unsigned tk = 0;
+  if constexpr (!SOLO) __syncthreads();
+  if (threadIdx.x < R && (am >> threadIdx.x & 1))
+    tk = __hip_atomic_fetch_add(ctr_of(threadIdx.x), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if constexpr (!SOLO) {
+    if (threadIdx.x < R) s_ticket[threadIdx.x] = tk;
+    __syncthreads();
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (!(am >> r & 1)) continue;
+    const unsigned ticket = SOLO ? (unsigned)__builtin_amdgcn_readlane((int)tk, r) : s_ticket[r];
+    if (ticket != (unsigned)(n_splits - 1)) continue;
+    if (has_item) {  // attn_body's combine
+      const __amdgpu_buffer_rsrc_t wrs = ws_rsrc(r);
+      const unsigned hoff = (unsigned)(hq * n_splits * (HS + 4)) * 4;
+      float mx = -INFINITY, lt = 0.0f, ot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int s0 = 0; s0 < n_splits; s0 += 8) {
+        float4 ml[8], o4[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const unsigned off = hoff + (unsigned)(min(s0 + u, n_splits - 1) * (HS + 4)) * 4;
+          ml[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrs, off, 0, 16));
+          o4[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrs, off + 16 + dq * 16, 0, 16));
+        }
+        float nm = mx;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          if (s0 + u >= n_splits) ml[u].x = -INFINITY;
+          nm = fmaxf(nm, ml[u].x);
+        }
+        const float c = __builtin_amdgcn_exp2f(mx - nm);
+        lt = mul_rn(lt, c);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ot[i] = mul_rn(ot[i], c);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const float e = __builtin_amdgcn_exp2f(ml[u].x - nm);
+          lt = fmaf(ml[u].y, e, lt);
+          ot[0] = fmaf(o4[u].x, e, ot[0]);
+          ot[1] = fmaf(o4[u].y, e, ot[1]);
+          ot[2] = fmaf(o4[u].z, e, ot[2]);
+          ot[3] = fmaf(o4[u].w, e, ot[3]);
+        }
+        mx = nm;
+      }
+      uint16_t* yr = y + ((size_t)(b0 + r) * n_head + slice0 + hq) * HS + dq * 4;
+      *(uint2*)yr = make_uint2(pack2(ot[0] / lt, ot[1] / lt), pack2(ot[2] / lt, ot[3] / lt));
+    }
+    if (threadIdx.x == 0) __hip_atomic_store(ctr_of(r), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+  }
+}
+
 // The window's KV-append: roped k and v of row r into cache row pos0[0] + r of every group, with the fused kernel's
 // own rope8 (and, for fp8 caches, its kv8_quantize8) on the same operands: the same bits, codes and scales it stores
 // at T = 1. Grid (G, M), one wave: lanes 0..HS/8-1 (row group 0) rope k, the next HS/8 (row group 1) carry v. A row
@@ -885,9 +1244,30 @@ __global__ void __launch_bounds__(512, 1) attn_prefill_pair_kernel(const uint16_
 #define LGA_ATTN_Q8 2, 4
 #endif
 
+// rows per workgroup of the SHARED form by heads per workgroup: the largest value up to 4 (the product's MAX_BATCH; a
+// row slot that stays empty still costs its registers) that compiles with no scratch. One head compiles clean beyond 4
+// (R = 8 at 4 waves, R = 5 at 8 waves); 4 and 8 heads spill at R = 2. DESIGN.md 4.5f has the resource table
+#ifndef LGA_SHARED_R1
+#define LGA_SHARED_R1 4
+#endif
+#ifndef LGA_SHARED_R1_FEW
+#define LGA_SHARED_R1_FEW 4
+#endif
+#ifndef LGA_SHARED_R2
+#define LGA_SHARED_R2 4
+#endif
+#ifndef LGA_SHARED_R4
+#define LGA_SHARED_R4 1
+#endif
+#ifndef LGA_SHARED_R8
+#define LGA_SHARED_R8 1
+#endif
+static constexpr int attn_nw(int /*unr*/, int nw) { return nw; }
+
 // One attention call as the entry points describe it. kRows: lga_attention (q (T, H, hs) already roped, no append);
-// the other three are the fused decode forms on the qkv projection rows (the FUSED / WINDOW / BATCH comments above).
-enum AttnForm { kRows, kOne, kWindow, kBatch };
+// the other four are the fused decode forms on the qkv projection rows (the FUSED / WINDOW / BATCH / SHARED comments
+// above).
+enum AttnForm { kRows, kOne, kWindow, kBatch, kShared };
 struct AttnCall {
   const char* name;  // the entry point, for its messages
   AttnForm form;
@@ -902,11 +1282,12 @@ struct AttnCall {
   void* y;
   float* ws;
   unsigned* cnt;
-  long long slot_stride, scale_slot_stride;  // kBatch: elements between two sequences' caches / scale rows
+  long long slot_stride, scale_slot_stride;  // kBatch, kShared: elements between two sequences' caches / scale rows
   const int32_t* active;                     // kBatch: idle flags, may be null
   int H, G, hs, rope_n_elem, max_seq, n_splits;
   float scale;
   hipStream_t stream;
+  const int64_t* prefix_len = nullptr;  // kShared: the shared prefix's length, on the device
 };
 
 // the kernel instantiation of a call, one (heads per workgroup, keys in flight, waves) configuration: hs 64 exists
@@ -934,6 +1315,7 @@ static void attn_launch_cfg(const AttnCall& c, dim3 grid, int hsplit) {
       case kOne: LGA_FUSED(false, false);
       case kWindow: LGA_FUSED(false, true);
       case kBatch: LGA_FUSED(true, false);
+      case kShared:  // (launched by attn_launch itself: attn_shared_kernel)
       case kRows: break;
     }
   }
@@ -962,11 +1344,12 @@ static int attn_hsplit(int T, int G, int qpk, int n_splits) {
 // append, the grid, the kernel.
 static int attn_launch(const AttnCall& c) {
   const bool fused = c.form != kRows;
-  const bool many = c.form == kWindow || c.form == kBatch;
+  const bool slots = c.form == kBatch || c.form == kShared;  // the caches of all slots, slot_stride apart
+  const bool many = c.form == kWindow || slots;
   const int qpk = c.G > 0 ? c.H / c.G : 0;
   const long long seq_rows = (long long)c.G * c.max_seq;
   const bool ptrs = c.q && c.kc && c.vc && c.pos && c.y && (!fused || (c.rope_pos && c.cos && c.sin)) &&
-                    (!c.kv8 || (c.ksc && c.vsc));
+                    (!c.kv8 || (c.ksc && c.vsc)) && (c.form != kShared || c.prefix_len);
   const char* bad =
       !ptrs ? "null pointer"
       : many && !(c.rows >= 1 && c.rows <= 8) ? (c.form == kWindow ? "M must be in [1, 8]" : "B must be in [1, 8]")
@@ -978,7 +1361,7 @@ static int attn_launch(const AttnCall& c) {
       : fused && !(c.rope_rows > 0 && c.max_seq > 0) ? "empty rope cache or kv cache"
       : !(c.n_splits >= 1 && c.n_splits <= 256) ? "n_splits must be in [1, 256]"
       : !(c.n_splits == 1 || (c.ws && c.cnt)) ? "split attention needs workspace + counters"
-      : c.form == kBatch && c.slot_stride < seq_rows * c.hs
+      : slots && c.slot_stride < seq_rows * c.hs
           ? "slot_stride below one sequence's G * max_seq * head_size elements"
       : c.form == kBatch && c.kv8 && c.scale_slot_stride < seq_rows
           ? "scale_slot_stride below one sequence's G * max_seq scales"
@@ -1017,6 +1400,24 @@ static int attn_launch(const AttnCall& c) {
     if (c.hs == 128) attn_launch_cfg<128, QPK, CFG>(c, grid, hsplit);       \
     else attn_launch_cfg<64, QPK, CFG>(c, grid, hsplit);                    \
   } while (0)
+  if (c.form == kShared) {  // the same (UNR, NW) per heads-per-workgroup as below, R rows per workgroup
+#define LGA_SHARED(QPK, R, CFG)                                                                                      \
+  attn_shared_kernel<128, QPK, CFG, R><<<dim3(c.n_splits, c.G * hsplit, (c.rows + R - 1) / R), attn_nw(CFG) * 64, 0, \
+                                         c.stream>>>(                                                                \
+      (const uint16_t*)c.q, (uint16_t*)c.kc, (uint16_t*)c.vc, c.pos, c.prefix_len, (uint16_t*)c.y, c.ws, c.cnt, c.H, \
+      c.max_seq, c.scale, c.cos, c.sin, c.rope_rows, hsplit, (long)c.slot_stride, c.active, c.rows)
+    switch (qpk / hsplit) {
+      case 1:
+        if (c.G * hsplit <= 16) LGA_SHARED(1, LGA_SHARED_R1_FEW, LGA_ATTN_Q1_FEW);
+        else LGA_SHARED(1, LGA_SHARED_R1, LGA_ATTN_Q1);
+        break;
+      case 2: LGA_SHARED(2, LGA_SHARED_R2, LGA_ATTN_Q2); break;
+      case 4: LGA_SHARED(4, LGA_SHARED_R4, LGA_ATTN_Q4); break;
+      default: LGA_SHARED(8, LGA_SHARED_R8, LGA_ATTN_Q8); break;  // (q_per_kv was checked above)
+    }
+#undef LGA_SHARED
+    LGA_LAUNCH_RETURN();
+  }
   switch (qpk / hsplit) {
     case 1:  // one head per group: 8 waves x 2 keys in flight when the groups are few (TP ranks: G = 4 7.9 vs 8.2 us,
              // G = 8 8.0 vs 8.7 at 16 splits; profiles/r04u_attn_head_slices.txt), else 4 x 4 (Llama-2-7B, G = 32)
@@ -1133,6 +1534,22 @@ extern "C" int lga_attention_decode_batch_kv8(const void* qkv, void* k_codes, vo
                                    k_scale, v_scale, cache_pos, rope_pos, cos, sin, rope_rows, y, workspace, counters,
                                    slot_stride, scale_slot_stride, active, n_head, n_query_groups, head_size,
                                    rope_n_elem, max_seq, n_splits, scale, stream});
+}
+
+// n samples of one prompt: the batch form for B rows at ONE position pos[0] (cache and rope position) whose keys j <
+// min(max(prefix_len[0], 0), pos[0]) only slot 0 holds; row b reads those from slot 0, the rest from slot b, and
+// appends to slot b. y and row pos[0] of every slot have the bits of lga_attention_decode_batch on caches whose slot b
+// holds slot 0's prefix rows, with the same n_splits. bf16 caches only.
+extern "C" int lga_attention_decode_shared(const void* qkv, void* k_cache, void* v_cache, const int64_t* pos,
+                                           const int64_t* prefix_len, const float* cos, const float* sin,
+                                           int rope_rows, void* y, float* workspace, unsigned* counters, int B,
+                                           long long slot_stride, const int32_t* active, int n_head,
+                                           int n_query_groups, int head_size, int rope_n_elem, int max_seq,
+                                           int n_splits, float scale, hipStream_t stream) {
+  return lga::attn_launch(AttnCall{"lga_attention_decode_shared", lga::kShared, false, B, qkv, k_cache, v_cache,
+                                   nullptr, nullptr, pos, pos, cos, sin, rope_rows, y, workspace, counters,
+                                   slot_stride, 0, active, n_head, n_query_groups, head_size, rope_n_elem, max_seq,
+                                   n_splits, scale, stream, prefix_len});
 }
 
 #ifdef LGA_ATTN_TRACE

@@ -327,6 +327,105 @@ def generate_batch(model: GPT, prompts: List[torch.Tensor], max_new_tokens: int,
     return [torch.cat([p, f, out[:n_b, b].to(p.dtype)]) for b, (p, f, n_b) in enumerate(zip(prompts, firsts, lengths))]
 
 
+# What ``generate_samples(share="auto")`` takes where the shared-prefix launch applies: True = that launch, False = the
+# copy route. Fixed by the rule of DESIGN §4.5f: the launch is picked only if it beat the batch launch per block at B =
+# 2 and B = 4 at all three measured positions by more than the runs' spread.
+SHARE_AUTO = False
+
+
+def _copy_prefix(model: GPT, P: int, B: int) -> None:
+    """Rows [0, P) of cache slot 0 into slots 1..B-1 of every layer (codes and scales too for the fp8 cache)."""
+    for block in model.transformer.h:
+        kv = block.attn.kv_cache
+        for t in (kv.k, kv.v) + ((kv.k_scale, kv.v_scale) if kv.fp8 else ()):
+            t[1:B, :, :P].copy_(t[:1, :, :P].expand(B - 1, *t.shape[1:2], P, *t.shape[3:]))
+
+
+@torch.inference_mode()
+def generate_samples(model: GPT, prompt: torch.Tensor, max_new_tokens: int, num_samples: int, *,
+                     temperature: float = 1.0, top_k: Optional[int] = None, top_p: float = 1.0,
+                     eos_id: Optional[int] = None, seeds: Optional[List[int]] = None, use_graph: bool = True,
+                     share="auto", wave: int = MAX_BATCH) -> List[torch.Tensor]:
+    """``num_samples`` completions of ONE prompt ((T,)), each ``max_new_tokens`` long at most, for one prefill: the
+    prompt goes into cache slot 0 once, the first token of sample i is drawn from that one logits row with
+    ``SamplerRNG(device, seeds[i])`` (its draw 0), and the samples decode together in waves of at most MAX_BATCH = 4
+    behind the same prefix; rows [0, T) of slot 0 are never rewritten. Sample i is exactly what ``generate(model,
+    prompt, T + max_new_tokens, ..., rng=SamplerRNG(device, seeds[i]))`` returns (at temperature 0 all are equal);
+    ``num_samples == 1`` is that call. ``seeds`` None: one per sample from torch's generator, in sample order.
+    ``share=True``: the wave's decode attention is the shared-prefix launch (``ops.attention_decode_shared``: the
+    prompt's K / V stay in slot 0 alone and every step reads them once per set of rows), ``NotImplementedError`` where
+    it does not apply (fp8 cache, a geometry outside the batch launch's). ``share=False``: the prompt's rows are copied
+    into the wave's other slots and the wave runs the batched step of ``generate_batch`` — everything that covers.
+    ``share="auto"``: the launch where it applies and ``SHARE_AUTO`` allows it, else the copies. Refuses what
+    ``generate_batch`` refuses, before any launch. ``wave``: samples per wave, 1..MAX_BATCH. A model that carries a
+    LoRA adapter set (``lit_gpt.lora.attach_many``) is refused too: a prefix depends on its adapter."""
+    if num_samples < 1:
+        raise ValueError("generate_samples: num_samples must be at least 1")
+    if not 1 <= wave <= MAX_BATCH:
+        raise NotImplementedError(f"generate_samples: waves of {wave}; the MI355X batched decode runs 1..{MAX_BATCH} "
+                                  "sequences per step")
+    if share not in (True, False, "auto"):
+        raise ValueError(f"generate_samples: share must be True, False or 'auto', got {share!r}")
+    if max_new_tokens < 1:
+        raise ValueError("generate_samples: max_new_tokens must be at least 1")
+    if seeds is not None and len(seeds) != num_samples:
+        raise ValueError(f"generate_samples: {len(seeds)} seeds for {num_samples} samples")
+    if getattr(model, "lora_adapters", None) is not None:
+        raise NotImplementedError("generate_samples: a model with a LoRA adapter set (a prefix depends on its adapter)")
+    if top_p != 1.0:
+        _check_model_top_p("generate_samples", model, top_p, temperature, top_k)
+        if temperature == 0.0:
+            top_p = 1.0
+    tp = _top_p_kw(top_p)
+    T = prompt.size(0)
+    if model.max_seq_length < T + max_new_tokens - 1:
+        raise NotImplementedError(f"max_seq_length {model.max_seq_length} needs to be >= {T + max_new_tokens - 1}")
+    device = prompt.device
+    sampling = temperature > 0.0
+    B = min(num_samples, wave)
+    if B > 1 and sampling and not graph_sampling(model, temperature, top_k, **tp):
+        raise NotImplementedError("generate_samples: sampling several samples runs on the device sampler only "
+                                  f"(temperature > 0 with top_k in [1, {ops.MAX_TOP_K}] over bf16 logits)")
+    if sampling and seeds is None:
+        seeds = [int(torch.randint(0, 2**62, (1,))) for _ in range(num_samples)]  # as SamplerRNG draws its own
+    rngs = [SamplerRNG(device, s) for s in seeds] if sampling else None
+    if num_samples == 1:
+        return [generate(model, prompt, T + max_new_tokens, temperature=temperature, top_k=top_k, eos_id=eos_id,
+                         use_graph=use_graph, rng=None if rngs is None else rngs[0], **tp)]
+    model._batch_check(B)  # before any launch
+    kv = model.transformer.h[0].attn.kv_cache
+    applies = (model.transformer.h[0].attn.batch_fusable(model.transformer.wte.weight.dtype)
+               and not (kv is not None and kv.fp8))
+    if share is True and not applies:
+        raise NotImplementedError("generate_samples(share=True): the shared-prefix decode attention needs the bf16 KV "
+                                  "cache and the batched decode attention's geometry (head_size == rope_n_elem == "
+                                  "128, 1 / 2 / 4 / 8 heads per query group, bf16 activations)")
+    shared = applies and (share is True or (share == "auto" and SHARE_AUTO))
+    if kv is None or kv.k.size(0) < B:
+        model.set_kv_cache(batch_size=B, device=device, dtype=None if kv is None else kv.cache_dtype)
+    logits = model(prompt.view(1, -1), torch.arange(0, T, device=device), last_token_only=True, kv_slot=0)
+    firsts = [sample(logits, temperature=temperature, top_k=top_k, rng=None if rngs is None else rngs[i],
+                     **tp).to(dtype=prompt.dtype).clone() for i in range(num_samples)]
+    n_steps = max_new_tokens - 1
+    if n_steps <= 0:
+        return [torch.cat([prompt, f]) for f in firsts]
+    from lit_gpt.runtime import BatchDecodeGraph
+
+    if not shared:
+        _copy_prefix(model, T, B)
+    prefix = torch.tensor([T], dtype=torch.int64, device=device) if shared else None
+    ys: List[torch.Tensor] = []
+    for w in range(0, num_samples, B):  # a wave: up to ``wave`` samples in slots 0.. behind the one prefix
+        nb = min(B, num_samples - w)
+        dg = BatchDecodeGraph(model, torch.cat(firsts[w:w + nb]), [T] * nb,
+                              chunk=DECODE_CHUNK if use_graph and n_steps > DECODE_CHUNK else 1,
+                              temperature=temperature, top_k=top_k, rngs=None if rngs is None else rngs[w:w + nb],
+                              use_graph=use_graph, **({"shared_prefix": prefix} if shared and nb > 1 else {}), **tp)
+        out, lengths = _batch_steps(dg, n_steps, eos_id)
+        ys += [torch.cat([prompt, firsts[w + b], out[:n_b, b].to(prompt.dtype)]) for b, n_b in enumerate(lengths)]
+    return ys
+
+
 @torch.inference_mode()
 def generate_continuous(model: GPT, prompts: List[torch.Tensor], max_new_tokens, *, batch_size: int = MAX_BATCH,
                         temperature: float = 1.0, top_k: Optional[int] = None, eos_id: Optional[int] = None,
@@ -542,8 +641,13 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
          checkpoint_dir: Path = Path("checkpoints/stabilityai/stablelm-base-alpha-3b"),
          quantize: Optional[str] = None, precision: Optional[str] = None, compile: bool = False,
          synthetic: Optional[str] = None, prompt_len: int = 16, batch_size: int = 1,
-         kv_cache: str = "bf16", prompts_file: Optional[Path] = None, top_p: float = 1.0) -> None:
+         kv_cache: str = "bf16", prompts_file: Optional[Path] = None, top_p: float = 1.0,
+         share_prompt: bool = False) -> None:
     precision = precision or "bf16-true"
+    if share_prompt and batch_size <= 1:
+        raise ValueError("--share_prompt decodes the samples of one prompt together: it needs --batch_size > 1")
+    if share_prompt and prompts_file is not None:
+        raise ValueError("--share_prompt serves the samples of ONE prompt: it cannot be combined with --prompts_file")
     if not 0.0 < top_p <= 1.0:
         raise ValueError(f"--top_p must be in (0, 1], got {top_p}")
     tp = _top_p_kw(top_p)
@@ -599,6 +703,24 @@ def main(prompt: str = "What food do llamas eat?", *, num_samples: int = 1, max_
         tokens_generated = sum(y.size(0) - e.size(0) for y, e in zip(ys, many))
         print(f"Time for inference of {len(many)} prompts through {min(batch_size, len(many))} slots: {t:.02f} sec "
               f"total, {tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
+        print(f"Memory used: {torch.cuda.max_memory_allocated() / 1e9:.02f} GB", file=sys.stderr)
+        return
+    if share_prompt:
+        # --share_prompt: all samples behind one prefill of the prompt (generate_samples), --batch_size at a time; the
+        # seeds are drawn in the order the loop below draws them, so the samples are the same
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys = generate_samples(model, encoded, max_new_tokens, num_samples, temperature=temperature, top_k=top_k,
+                              eos_id=eos_id, wave=batch_size, **tp)
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        for block in model.transformer.h:
+            block.attn.kv_cache.reset_parameters()
+        for y in ys:
+            print(tokenizer.decode(y) if tokenizer is not None else y.tolist())
+        tokens_generated = sum(y.size(0) - prompt_length for y in ys)
+        print(f"Time for inference of {num_samples} samples of one prompt: {t:.02f} sec total, "
+              f"{tokens_generated / t:.02f} tokens/sec", file=sys.stderr)
         print(f"Memory used: {torch.cuda.max_memory_allocated() / 1e9:.02f} GB", file=sys.stderr)
         return
     for i in range(0, num_samples if batch_size > 1 else 0, batch_size):
@@ -660,11 +782,14 @@ def _cli(argv=None) -> None:
                         "--batch_size slots with continuous batching (generate_continuous)")
     p.add_argument("--kv_cache", default="bf16", choices=sorted(KV_CACHE_DTYPES),
                    help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per row (0.516 x the bytes)")
+    p.add_argument("--share_prompt", action="store_true",
+                   help="with --batch_size > 1: prefill the prompt once for all --num_samples samples "
+                        "(generate_samples) instead of once per sample")
     a = p.parse_args(argv)
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,
          compile=a.compile, synthetic=a.synthetic, prompt_len=a.prompt_len, batch_size=a.batch_size,
-         kv_cache=a.kv_cache, prompts_file=a.prompts_file, top_p=a.top_p)
+         kv_cache=a.kv_cache, prompts_file=a.prompts_file, top_p=a.top_p, share_prompt=a.share_prompt)
 
 
 if __name__ == "__main__":

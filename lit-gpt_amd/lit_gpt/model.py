@@ -92,7 +92,8 @@ class GPT(nn.Module):
 
     def forward(self, idx: torch.Tensor, input_pos: Optional[torch.Tensor] = None, *,
                 last_token_only: bool = False, embedded: Optional[torch.Tensor] = None,
-                hidden_only: bool = False, kv_slot: int = 0, active: Optional[torch.Tensor] = None) -> torch.Tensor:
+                hidden_only: bool = False, kv_slot: int = 0, active: Optional[torch.Tensor] = None,
+                shared_prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(B=1, T) ids -> (1, T, padded_vocab) logits; ``last_token_only`` computes only the last row (1, 1, V)
         — all that ``generate`` samples from (generate/base.py:31). ``embedded`` (T * n_embd bf16) is
         ``transformer.wte(idx)`` already gathered — by the previous decode step's ``ops.argmax_embed`` in
@@ -104,7 +105,10 @@ class GPT(nn.Module):
         B = 1 prefill on slot b at the shared ``input_pos`` (T,); T = 1 is one batched decode step, ``input_pos`` (1,)
         shared or (B,) / (B, 1) one position per sequence, ``embedded`` (B * n_embd). Row b has the bits of the B = 1
         call on that sequence. ``active`` (B,) int32 on the device (batched decode step only, B >= 1): a row flagged 0 is
-        idle — its cache slot is left untouched and its logits are not meaningful."""
+        idle — its cache slot is left untouched and its logits are not meaningful. ``shared_prefix`` (1,) int64 on the
+        device (batched decode step only): the rows are samples of ONE prompt at one shared position, and the keys below
+        that length are read from slot 0 alone (``CausalSelfAttention.decode_rows``); the logits are those of the step
+        without it on caches whose every slot holds the prompt."""
         B, T = idx.shape
         if self.max_seq_length < T:
             raise ValueError(f"Cannot forward sequence of length {T}, max seq length is only {self.max_seq_length}.")
@@ -112,8 +116,9 @@ class GPT(nn.Module):
             raise TypeError("You need to call `gpt.set_kv_cache()`")
         if not idx.is_cuda:
             _gpu_only("GPT.forward")
-        if B != 1 or active is not None:  # (a one-slot engine, B = 1 with ``active``, is a batched step of one row)
-            return self._forward_batch(idx, input_pos, last_token_only, embedded, hidden_only, active)
+        if B != 1 or active is not None or shared_prefix is not None:
+            # (a one-slot engine, B = 1 with ``active``, is a batched step of one row)
+            return self._forward_batch(idx, input_pos, last_token_only, embedded, hidden_only, active, shared_prefix)
         cos, sin = self._rope_tables()
         if input_pos is not None:
             input_pos = input_pos.to(device=idx.device, dtype=torch.int64).contiguous()
@@ -231,7 +236,8 @@ class GPT(nn.Module):
         ln = self.transformer.ln_f
         return _lin(self.lm_head, x, norm_weight=ln.weight, norm_eps=ln.eps, rows=True)
 
-    def _forward_batch(self, idx, input_pos, last_token_only, embedded, hidden_only, active=None) -> torch.Tensor:
+    def _forward_batch(self, idx, input_pos, last_token_only, embedded, hidden_only, active=None,
+                       shared_prefix=None) -> torch.Tensor:
         """The B > 1 forms of ``forward`` (its docstring). T = 1 per block: the rows qkv GEMV with norm_1 fused, the
         decode attention of every sequence on its own cache slot (one batch launch, ``CausalSelfAttention.decode_rows``;
         ``active`` flags idle rows), the rows out-projection + residual, the
@@ -246,8 +252,8 @@ class GPT(nn.Module):
             raise ValueError(f"batch size {B} needs set_kv_cache(batch_size >= {B})")
         input_pos = input_pos.to(device=idx.device, dtype=torch.int64)
         if T > 1:  # the reference's shared positions: each row is the B = 1 prefill on its slot
-            if embedded is not None or active is not None:
-                raise ValueError("embedded / active: one token per sequence (T = 1) only")
+            if embedded is not None or active is not None or shared_prefix is not None:
+                raise ValueError("embedded / active / shared_prefix: one token per sequence (T = 1) only")
             return torch.cat([self.forward(idx[b:b + 1], input_pos, last_token_only=last_token_only,
                                            hidden_only=hidden_only, kv_slot=b) for b in range(B)])
         if input_pos.numel() == 1:
@@ -259,9 +265,31 @@ class GPT(nn.Module):
                              f"decode step, got shape {tuple(input_pos.shape)}")
         if active is not None and (active.numel() != B or active.dtype != torch.int32 or active.device != idx.device):
             raise ValueError(f"active must hold {B} int32 flags on the model's device")
+        if shared_prefix is not None:
+            if input_pos.numel() != 1:
+                raise ValueError("shared_prefix: the samples of one prompt sit at ONE position, input_pos (1,)")
+            if (shared_prefix.numel() != 1 or shared_prefix.dtype != torch.int64
+                    or shared_prefix.device != idx.device):
+                raise ValueError("shared_prefix must be one int64 length on the model's device")
+            self._shared_check()
+            pos = input_pos.reshape(1).contiguous()
         return self._rows_step(idx, embedded, hidden_only,
-                               lambda attn, x, cos, sin, **kw: attn.decode_rows(x, cos, sin, pos, active=active, **kw)
+                               lambda attn, x, cos, sin, **kw: attn.decode_rows(x, cos, sin, pos, active=active,
+                                                                                shared_prefix=shared_prefix, **kw)
                                ).view(B, 1, -1)
+
+    def _shared_check(self) -> None:
+        """What a shared-prefix step (``forward(..., shared_prefix=)``) needs beyond ``_batch_check``: the bf16 cache
+        and the batch launch's geometry in every block. Refused here, before any launch."""
+        for blk in self.transformer.h:
+            kv = blk.attn.kv_cache
+            if kv is not None and kv.fp8:
+                raise NotImplementedError("a shared prompt prefix over an fp8 KV cache: the shared-prefix decode "
+                                          "attention reads bf16 caches only")
+            if not blk.attn.batch_fusable(self.transformer.wte.weight.dtype):
+                raise NotImplementedError("a shared prompt prefix needs the batched decode attention launch: head_size "
+                                          "== rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group, bf16 "
+                                          "activations")
 
     @classmethod
     def from_name(cls, name: str, **kwargs: Any) -> "GPT":
@@ -463,13 +491,15 @@ class CausalSelfAttention(nn.Module):
             ws = wss[rows] = ops.AttentionWorkspace(rows, H, G, hs, n_splits, dev)
         return cos, sin, n_splits, ws
 
-    def _decode_attention(self, form, qkv, cache, pos, rope_pos, cos, sin, active=None, out=None) -> torch.Tensor:
+    def _decode_attention(self, form, qkv, cache, pos, rope_pos, cos, sin, active=None, out=None,
+                          prefix_len=None) -> torch.Tensor:
         """RoPE + KV-append + split decode attention of the rows of ``qkv`` in one launch of the form ``form`` ("fused",
-        "window" or "batch": ``ops._attention_decode``) over ``cache`` (``_cache``) -> (rows, H * hs)."""
+        "window", "batch" or "shared", the last behind ``prefix_len``: ``ops._attention_decode``)
+        over ``cache`` (``_cache``) -> (rows, H * hs)."""
         c = self.config
         cos, sin, n_splits, ws = self._decode_setup(qkv, cache, cos, sin)
         return ops._attention_decode(form, qkv, cache, pos, rope_pos, cos, sin, c.n_head, c.n_query_groups, c.head_size,
-                                     c.rope_n_elem, 1.0 / math.sqrt(c.head_size), n_splits, ws, out, active)
+                                     c.rope_n_elem, 1.0 / math.sqrt(c.head_size), n_splits, ws, out, active, prefix_len)
 
     def _attend(self, qkv, cache, pos, rope_pos, cos, sin, out=None) -> torch.Tensor:
         """RoPE + KV-append + causal attention of the T rows of ``qkv`` over one sequence's ``cache`` -> (T, H * hs)."""
@@ -512,17 +542,28 @@ class CausalSelfAttention(nn.Module):
                 and c.n_head // c.n_query_groups in (1, 2, 4, 8) and dtype == torch.bfloat16)
 
     def decode_rows(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, *,
-                    norm: "RMSNorm", residual: torch.Tensor, active: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    norm: "RMSNorm", residual: torch.Tensor, active: Optional[torch.Tensor] = None,
+                    shared_prefix: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Batched decode step: x (B, C), one token of each of B sequences at ``pos`` (B,). The qkv and the
         out-projection run once for all rows (multi-row GEMVs); attention cannot share anything across sequences
         (each has its own K / V): on the fused decode form's geometry it is ONE ``ops.attention_decode_batch`` launch
         whose row b is the one-sequence launch on row b of qkv and cache slot b (``batch_attention``; the split count
         is the one-sequence step's, the bits of y depend on it), otherwise the one-sequence decode attention once per
         sequence, all through the one ``AttentionWorkspace`` (serial launches; its counters re-arm). ``active`` (B,)
-        int32 marks idle rows (0): their cache slot is untouched and their y is zero — the batch launch only."""
+        int32 marks idle rows (0): their cache slot is untouched and their y is zero — the batch launch only.
+        ``shared_prefix`` (1,) int64 on the device: the rows are samples of one prompt at the ONE position ``pos`` (1,),
+        and attention is ONE ``ops.attention_decode_shared`` launch that reads the keys below that length from slot 0
+        for all rows; bf16 cache and the batch launch's geometry only (``GPT._shared_check``)."""
         B = x.size(0)
         qkv = _lin(self.attn, x, norm_weight=norm.weight, norm_eps=norm.eps, rows=True)
         fusable = self.batch_fusable(qkv.dtype)
+        if shared_prefix is not None:
+            if not fusable or self.kv_cache.fp8:
+                raise NotImplementedError("a shared prompt prefix needs the bf16 cache and the batched decode "
+                                          "attention's geometry")
+            y = self._decode_attention("shared", qkv, self._cache(qkv.dtype), pos, pos, cos, sin, active=active,
+                                       prefix_len=shared_prefix)
+            return _lin(self.proj, y, residual=residual, rows=True)
         if active is not None and not fusable:
             raise NotImplementedError("idle rows (active) need the batched decode attention launch: head_size == "
                                       "rope_n_elem == 128, 1 / 2 / 4 / 8 heads per query group, bf16 activations")

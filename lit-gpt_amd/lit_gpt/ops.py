@@ -83,6 +83,8 @@ SIGNATURES = {
                                         _P],
     "lga_attention_decode_batch": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, ctypes.c_longlong, _P, _I, _I, _I, _I,
                                    _I, _I, _F, _P],
+    "lga_attention_decode_shared": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, ctypes.c_longlong, _P, _I, _I, _I, _I,
+                                    _I, _I, _F, _P],
     "lga_attention_decode_batch_kv8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, ctypes.c_longlong,
                                        ctypes.c_longlong, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "lga_kv8_rope_append": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -680,15 +682,19 @@ def _kv8(cache, name, dims=3):
 
 
 def _attention_decode(form, qkv, cache, pos, rope_pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale,
-                      n_splits, workspace, out, active=None):
-    """The six ``attention_decode_*`` functions: ``form`` is "fused" (one row), "window" (M rows of one sequence from
-    ``pos`` (1,)) or "batch" (B sequences, ``pos`` (B,), the caches of all slots); ``cache`` is (k, v) bf16 or (k codes,
-    v codes, k scales, v scales) fp8. Checks, workspace, one ``lga_attention_decode_*`` call; returns y."""
+                      n_splits, workspace, out, active=None, prefix_len=None):
+    """The seven ``attention_decode_*`` functions: ``form`` is "fused" (one row), "window" (M rows of one sequence from
+    ``pos`` (1,)), "batch" (B sequences, ``pos`` (B,), the caches of all slots) or "shared" (B samples of one prompt at
+    ``pos`` (1,) — their rope position too, ``rope_pos`` is not read — behind ``prefix_len`` (1,); bf16 only); ``cache`` is (k, v) bf16 or (k
+    codes, v codes, k scales, v scales) fp8. Checks, workspace, one ``lga_attention_decode_*`` call; returns y."""
     H, G, hs = n_head, n_query_groups, head_size
     fp8 = len(cache) == 4
     name = f"attention_decode_{form}" + ("_kv8" if fp8 else "")
     rows, kc = qkv.shape[0], cache[0]
-    R = {"fused": "T", "window": "M", "batch": "B"}[form]
+    R = {"fused": "T", "window": "M", "batch": "B", "shared": "B"}[form]
+    slots = form in ("batch", "shared")  # the caches of all slots
+    if form == "shared" and fp8:
+        raise NotImplementedError("attention_decode_shared reads bf16 caches only")
     if form == "fused":
         if rows != 1:
             raise ValueError(f"{name} handles exactly one token (T = 1)")
@@ -701,18 +707,23 @@ def _attention_decode(form, qkv, cache, pos, rope_pos, cos, sin, n_head, n_query
             raise ValueError(f"{name}: qkv rows must hold (H + 2G) * hs values")
     if form == "window" and pos.numel() != 1:
         raise ValueError(f"{name}: pos0 holds one position (row r sits at pos0 + r)")
-    if form == "batch":
+    if form == "shared":
+        if pos.numel() != 1:
+            raise ValueError(f"{name}: pos holds the one position all rows sit at, got {tuple(pos.shape)}")
+        if prefix_len is None or prefix_len.numel() != 1:
+            raise ValueError(f"{name}: prefix_len must be one int64 value on the device")
+    if slots:
         if kc.dim() != 4 or kc.shape[0] < rows or kc.shape[1] != G:
             raise ValueError(f"{name}: the caches are the whole (slots >= B, G, max_seq, hs) tensors, got "
                              f"{tuple(kc.shape)} for B = {rows}")
-        if pos.numel() != rows:
+        if form == "batch" and pos.numel() != rows:
             raise ValueError(f"{name}: pos holds one position per sequence ({rows}), got {tuple(pos.shape)}")
         if active is not None and (active.numel() != rows or active.dtype != torch.int32):
             raise ValueError(f"{name}: active must hold {rows} int32 flags")
         if cache[1].shape != kc.shape:
             raise ValueError(f"{name}: k_cache and v_cache must have one shape")
     if fp8:
-        ptrs = _kv8(cache, name, 4 if form == "batch" else 3)
+        ptrs = _kv8(cache, name, 4 if slots else 3)
     else:
         ptrs = _dev(kc, "k_cache", torch.bfloat16), _dev(cache[1], "v_cache", torch.bfloat16)
     y = out if out is not None else torch.empty(rows, H * hs, dtype=torch.bfloat16, device=qkv.device)
@@ -731,12 +742,13 @@ def _attention_decode(form, qkv, cache, pos, rope_pos, cos, sin, n_head, n_query
         ws, cnt = _dev(workspace.partials, "workspace", torch.float32), _dev(workspace.counters, "counters", torch.int32)
     args = [_dev(qkv, "qkv", torch.bfloat16), *ptrs, _dev(pos, "pos", torch.int64)]
     if form != "window":  # (a window's rope positions are its cache positions, pos0 + r)
-        args.append(_dev(rope_pos, "rope_pos", torch.int64))
+        args.append(_dev(prefix_len, "prefix_len", torch.int64) if form == "shared"
+                    else _dev(rope_pos, "rope_pos", torch.int64))
     args += [_dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32), cos.shape[0],
              _dev(y, "y", torch.bfloat16), ws, cnt]
     if form != "fused":
         args.append(rows)
-    if form == "batch":  # the slot strides (of the scale rows too), the idle flags
+    if slots:  # the slot strides (of the scale rows too), the idle flags
         args += [kc.stride(0)] + ([cache[2].stride(0)] if fp8 else []) + [_opt(active, "active", torch.int32)]
     _check(getattr(load_library(), "lga_" + name)(*args, H, G, hs, rope_n_elem, kc.shape[-2], n_splits, float(scale),
                                                   _stream()))
@@ -817,6 +829,18 @@ def attention_decode_batch(qkv, k_cache, v_cache, pos, cos, sin, n_head, n_query
     untouched); None runs every row."""
     return _attention_decode("batch", qkv, (k_cache, v_cache), pos, pos, cos, sin, n_head, n_query_groups, head_size,
                              rope_n_elem, scale, n_splits, workspace, out, active)
+
+
+def attention_decode_shared(qkv, k_cache, v_cache, pos, prefix_len, cos, sin, n_head, n_query_groups, head_size,
+                            rope_n_elem, scale, n_splits=1, workspace: Optional[AttentionWorkspace] = None, active=None,
+                            out=None):
+    """One decode token of each of B = qkv.shape[0] (1..8) samples of ONE prompt in one launch: every row sits at
+    ``pos[0]`` and the keys below ``prefix_len[0]`` (both (1,) int64, read on the device) are held by slot 0 alone. Row b
+    reads them there, its own later keys in slot b, and appends to slot b. y (B, H*hs) and row pos[0] of every slot are
+    bit-identical to ``attention_decode_batch`` on caches whose slot b holds slot 0's prefix rows; those rows of slots
+    1.. are never touched. ``active`` as in the batch form. bf16 caches only."""
+    return _attention_decode("shared", qkv, (k_cache, v_cache), pos, pos, cos, sin, n_head, n_query_groups,
+                             head_size, rope_n_elem, scale, n_splits, workspace, out, active, prefix_len)
 
 
 def attention_decode_batch_kv8(qkv, cache, pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale,

@@ -235,15 +235,17 @@ class BatchDecodeGraph:
 
     def __init__(self, model, first_tokens: torch.Tensor, first_pos, chunk: int = 1, *, temperature: float = 0.0,
                  top_k: Optional[int] = None, rngs=None, use_graph: bool = True, top_p: float = 1.0,
-                 adapters=None) -> None:
+                 adapters=None, shared_prefix: Optional[torch.Tensor] = None) -> None:
         """``first_tokens`` (B,): each sequence's newest token; ``first_pos``: its position per sequence. Runs one
         real step eagerly, then captures. ``use_graph=False`` keeps every step eager (tests A/B the two).
+        ``shared_prefix`` (1,) int64 on the device: the sequences are samples of one prompt at one position whose keys
+        below that length only cache slot 0 holds (``GPT.forward(..., shared_prefix=)``); the step reads ``pos[0]``.
         ``adapters``: per sequence the index of its LoRA adapter in ``model.lora_adapters`` (lora.attach_many) or None,
         written to the set's device-resident row ids before the first step."""
         dev = first_tokens.device
         B = first_tokens.numel()
         _assign_adapters(model, adapters, B)
-        self.model, self.B = model, B
+        self.model, self.B, self.shared_prefix = model, B, shared_prefix
         self.temperature, self.top_k, self.rngs, self.top_p = float(temperature), top_k, rngs, float(top_p)
         if self.temperature > 0.0 and (rngs is None or len(rngs) != B
                                        or not _sampling_ok(self.temperature, top_k, self.top_p)):
@@ -276,7 +278,11 @@ class BatchDecodeGraph:
 
     def _step_body(self, idx_out: Optional[torch.Tensor] = None, embedded: bool = True) -> None:
         model, B = self.model, self.B
-        logits = model(self.token.view(B, 1), self.pos, embedded=self.x_emb if embedded else None).view(B, -1)
+        if self.shared_prefix is None:
+            logits = model(self.token.view(B, 1), self.pos, embedded=self.x_emb if embedded else None).view(B, -1)
+        else:  # the samples advance in lock step: every pos[b] is pos[0]
+            logits = model(self.token.view(B, 1), self.pos[:1], embedded=self.x_emb if embedded else None,
+                           shared_prefix=self.shared_prefix).view(B, -1)
         table = model.transformer.wte.weight
         for b in range(B):
             out = None if idx_out is None else idx_out[b:b + 1]

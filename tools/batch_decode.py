@@ -18,6 +18,16 @@ usage: python tools/batch_decode.py kernels [--out FILE.json]
            Mixtral (H = 32, G = 8, S = 32768, p around 32066) geometries, bf16 and fp8 caches. One graph of 32 launches
            (32 x B for the loop) over distinct cache copies per form, so K / V comes from HBM; the two graphs are
            replayed alternately, 9 times each, device events around each replay; median and min..max are reported.
+       python tools/batch_decode.py attn --shared [--out FILE.json]
+           DESIGN §4.5f: us per block of ONE lga_attention_decode_shared launch against ONE lga_attention_decode_batch
+           launch, B = 2, 4 samples behind a 2048-token prefix at p = 2048, 2175, 2302 (S = 2304), Llama-2-7B (H = G =
+           32) and one GQA geometry (H = 32, G = 8). Same method: graphs of 32 launches over distinct cache copies,
+           replayed alternately 9 times each. Prints the rule for generate_samples(share="auto").
+       python tools/batch_decode.py samples [--samples 4] [--prompt_len 2048] [--steps 255] [--out FILE.json]
+           DESIGN §4.5f: N samples of one prompt end to end, synthetic Llama-2-7B int4-g128, greedy: generate_samples
+           with share=True, with share=False, and generate_batch([prompt] * N) (one prefill per sample), alternated run
+           by run, 3 runs each after a warm-up of each. Wall time with the prefill, and decode tokens/s with the
+           prefill-only run of each route subtracted.
        python tools/batch_decode.py continuous [--out FILE.json]
            DESIGN §4.5e (c): 16 synthetic requests (Llama-2-7B int4-g128, 512-token prompts, budgets from a fixed list
            spanning 32..256) through 4 slots with generate_continuous against the same requests through
@@ -226,6 +236,120 @@ def attn(out):
     _write(out, result)
 
 
+SHARED_GEOMS = {"llama-2-7b": (32, 32), "gqa-32x8": (32, 8)}  # H, G
+SHARED_S, SHARED_P, SHARED_POS = 2304, 2048, (2048, 2175, 2302)
+
+
+def attn_shared(out):
+    import math
+
+    dev = torch.device("cuda")
+    hs, slots, S = 128, 4, SHARED_S
+    sc = 1.0 / math.sqrt(hs)
+    result = {"what": "us per block: one lga_attention_decode_shared launch vs one lga_attention_decode_batch launch, "
+                      f"B samples at one position p behind a {SHARED_P}-token prefix, S = {S}; graphs of 32 blocks "
+                      "over distinct cache copies, replayed alternately 9 times each, device events around each replay",
+              "cases": {}}
+    for gname, (H, G) in SHARED_GEOMS.items():
+        n_splits = ops.decode_splits(G, H // G, hs, S)
+        cos = torch.randn(S, hs, device=dev)
+        sin = torch.randn(S, hs, device=dev)
+        qkv = torch.randn(slots, (H + 2 * G) * hs, device=dev).bfloat16()
+        one = slots * G * S * hs * 2 * 2  # bytes of one (k, v) copy of all slots
+        copies = max(2, min(ATTN_BLOCKS, int(3.0e9 // one)))
+        caches = [tuple(torch.randn(slots, G, S, hs, device=dev).bfloat16() for _ in "kv") for _ in range(copies)]
+        pre = torch.tensor([SHARED_P], device=dev)
+        for B in (2, 4):
+            ws = ops.AttentionWorkspace(B, H, G, hs, n_splits, dev)
+            y = torch.empty(B, H * hs, device=dev, dtype=torch.bfloat16)
+            q = qkv[:B].contiguous()
+            for p in SHARED_POS:
+                pos1 = torch.tensor([p], device=dev)
+                posB = torch.full((B,), p, device=dev)
+
+                def shared():
+                    for i in range(ATTN_BLOCKS):
+                        c = caches[i % copies]
+                        ops.attention_decode_shared(q, c[0], c[1], pos1, pre, cos, sin, H, G, hs, hs, sc, n_splits,
+                                                    workspace=ws, out=y)
+
+                def batch():
+                    for i in range(ATTN_BLOCKS):
+                        c = caches[i % copies]
+                        ops.attention_decode_batch(q, c[0], c[1], posB, cos, sin, H, G, hs, hs, sc, n_splits,
+                                                   workspace=ws, out=y)
+
+                graphs = {}
+                for name, fn in (("shared", shared), ("batch", batch)):
+                    fn()
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        fn()
+                    graphs[name] = g
+                row = _alternate_us(graphs, ATTN_BLOCKS)
+                row.update(n_splits=n_splits, copies=copies,
+                           shared_faster_beyond_spread=bool(row["shared"]["max_us"] < row["batch"]["min_us"]))
+                key = f"{gname}/B{B}/p{p}"
+                result["cases"][key] = row
+                print(key, json.dumps(row), flush=True)
+                del graphs
+        del caches
+        torch.cuda.empty_cache()
+    c = result["cases"]
+    result["auto_picks_shared_by_rule"] = bool(all(c[f"llama-2-7b/B{B}/p{p}"]["shared_faster_beyond_spread"]
+                                                   for B in (2, 4) for p in SHARED_POS))
+    _write(out, result)
+
+
+def samples(out, n, prompt_len, steps):
+    from generate.base import build_model, generate_batch, generate_samples
+    from lit_gpt import Config
+
+    dev = torch.device("cuda")
+    cfg = Config.from_name("Llama-2-7b-hf")
+    model = build_model(cfg, quantize="int4-g128", device=dev, max_seq_length=prompt_len + steps + 1)
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    prompt = torch.randint(0, cfg.vocab_size, (prompt_len,), generator=g, dtype=torch.int32).to(dev)
+    model.set_kv_cache(batch_size=min(n, 4), device=dev)
+    routes = {"share_true": lambda new: generate_samples(model, prompt, new, n, temperature=0.0, share=True),
+              "share_false": lambda new: generate_samples(model, prompt, new, n, temperature=0.0, share=False),
+              "generate_batch": lambda new: [y for i in range(0, n, 4)
+                                             for y in generate_batch(model, [prompt] * min(4, n - i), new,
+                                                                     temperature=0.0)]}
+
+    def timed(fn, new):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ys = fn(new)
+        torch.cuda.synchronize()
+        assert len(ys) == n and all(y.numel() == prompt_len + new for y in ys)
+        return time.perf_counter() - t0, ys
+
+    ref = None
+    for name, fn in routes.items():  # warm-up of each; the three routes give the same tokens
+        _, ys = timed(fn, steps + 1)
+        ref = ref or ys
+        assert all(torch.equal(a, b) for a, b in zip(ys, ref)), name
+    full = {k: [] for k in routes}
+    pre = {k: [] for k in routes}
+    for _ in range(3):
+        for name, fn in routes.items():
+            full[name].append(timed(fn, steps + 1)[0])
+            pre[name].append(timed(fn, 1)[0])
+    result = {"what": f"{n} samples of one {prompt_len}-token prompt, {steps} decode steps, synthetic Llama-2-7B "
+                      "int4-g128, greedy; the three routes alternated run by run, 3 runs each after a warm-up of each; "
+                      "wall_s includes the prefill(s); decode = wall - the route's run of 1 new token",
+              "samples": n, "prompt_len": prompt_len, "steps": steps, "routes": {}}
+    for name in routes:
+        dec = [a - b for a, b in zip(full[name], pre[name])]
+        result["routes"][name] = {"wall_s_runs": full[name], "wall_s_median": statistics.median(full[name]),
+                                  "prefill_s_median": statistics.median(pre[name]), "decode_s_runs": dec,
+                                  "decode_tokens_per_s": n * steps / statistics.median(dec)}
+        print(name, json.dumps(result["routes"][name]), flush=True)
+    _write(out, result)
+
+
 CONT_BUDGETS = (256, 32, 64, 48, 128, 32, 96, 224, 40, 192, 32, 80, 160, 56, 112, 32)  # arrival order
 
 
@@ -344,7 +468,9 @@ def _write(out, result):
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
-    p.add_argument("mode", choices=("kernels", "e2e", "attn", "continuous"))
+    p.add_argument("mode", choices=("kernels", "e2e", "attn", "continuous", "samples"))
+    p.add_argument("--shared", action="store_true", help="attn: the shared-prefix launch against the batch launch")
+    p.add_argument("--samples", type=int, default=4, help="samples: samples of the one prompt")
     p.add_argument("--out", default=None)
     p.add_argument("--batches", default="1,2,4")
     p.add_argument("--prompt_len", type=int, default=2048)
@@ -357,7 +483,9 @@ if __name__ == "__main__":
     if a.mode == "kernels":
         kernels(a.out)
     elif a.mode == "attn":
-        attn(a.out)
+        (attn_shared if a.shared else attn)(a.out)
+    elif a.mode == "samples":
+        samples(a.out, a.samples, a.prompt_len, a.steps)
     elif a.mode == "continuous":
         continuous(a.out)
     else:
