@@ -1,4 +1,7 @@
-"""Per-kernel parity on the MI355X: every HIP op through the C-ABI against the CPU oracle.
+"""Per-kernel parity on the MI355X: the bf16 and quantized HIP ops through the C-ABI against the CPU oracle. The
+GPT-NeoX ops (lga_layernorm, lga_gelu), the fp32 path (csrc/fp32.hip, lga_argmax_f32, the fp32-row lga_embedding)
+are in tests/test_gpu_neox_kernels.py; the later kernel families have files of their own (test_gpu_int8.py,
+test_gpu_kv8.py, test_gpu_lora.py, ...).
 
 Integer / byte work (quantizer packing, KV append, argmax) must be bit-exact; fp kernels are checked against an
 fp64/fp32 reference of the same op on the same bf16 inputs with the tolerance written in each test.

@@ -146,3 +146,108 @@ def test_pythia160m_fp32_greedy_128_tokens_equal_reference():
         checked += 1
     assert checked >= 64, checked
     print(f"fp32: {checked} of 128 greedy tokens checked against the reference's fp32 run")
+
+
+# ------------------------------------------------------------------ the NeoX block at the geometries pythia-160m is not
+def _neox_cfg(kind):
+    from lit_gpt import Config
+
+    if kind == "pythia-14m":  # as registered: head_size 32, 8 rotary dims
+        return Config.from_name("pythia-14m")
+    if kind == "hs256":  # head_size 256, 64 rotary dims, as in pythia-1b
+        return Config(n_layer=2, n_embd=512, n_head=2, vocab_size=512, padding_multiple=64, block_size=64)
+    if kind == "falcon":  # MQA, one shared bias-free-Linear block norm, tanh GELU, full rotary; head_size 64
+        return Config(n_layer=2, n_embd=256, n_head=4, n_query_groups=1, shared_attention_norm=True, bias=False,
+                      gelu_approximate="tanh", rotary_percentage=1.0, vocab_size=512, padding_multiple=64,
+                      block_size=64)
+    raise KeyError(kind)
+
+
+NEOX_T, NEOX_STEPS = 9, 8  # an odd prompt length, then 8 teacher-forced decode steps
+
+
+def _neox_model(cfg, sd, dt):
+    from lit_gpt import GPT
+
+    model = GPT(cfg)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    model = model.to(device=DEV, dtype=dt)
+    model.max_seq_length = NEOX_T + NEOX_STEPS
+    model.set_kv_cache(1, device=DEV, dtype=dt)
+    return model.eval()
+
+
+def _neox_weights(cfg):
+    """oracle.synth's weights; its all-zero biases and all-one norm weights are moved off those values (a kernel
+    that dropped a bias or a norm weight would otherwise compute the same logits)."""
+    sd = synth.state_dict(cfg, seed=4321)
+    for k, v in sd.items():
+        if k.endswith(".bias") or (k.endswith(".weight") and v.ndim == 1):
+            sd[k] = (v + synth.normal(v.shape, k, 4321, 0.05)).astype(np.float32)
+    return sd
+
+
+def _teacher_forced(step, cfg):
+    """step(tokens (T,), positions (T,)) -> last-row logits; the prompt, then one token at a time."""
+    toks = torch.from_numpy(synth.token_ids(NEOX_T + NEOX_STEPS, cfg.vocab_size, seed=4321)).long()
+    out = [step(toks[:NEOX_T], torch.arange(NEOX_T))]
+    for i in range(NEOX_STEPS):
+        out.append(step(toks[NEOX_T + i:NEOX_T + i + 1], torch.tensor([NEOX_T + i])))
+    return out
+
+
+def _product_step(model):
+    return lambda t, p: model(t.view(1, -1).to(DEV), p.to(DEV))[0, -1].float().cpu()
+
+
+def _oracle_step(ref):
+    ref.set_kv_cache(NEOX_T + NEOX_STEPS)
+    return lambda t, p: ref.forward(t, p)[-1]
+
+
+@pytest.mark.parametrize("kind", ["pythia-14m", "hs256", "falcon"])
+@torch.inference_mode()
+def test_neox_fp32_geometries_match_float64_oracle(kind):
+    """--precision 32-true outside pythia-160m's geometry: head_size 32 with 8 rotary dims, head_size 256 with 64,
+    and a falcon-shaped block (MQA, shared attention norm, bias-free Linears, tanh GELU, full rotary). Last-row logits
+    of a 9-token prefill and 8 teacher-forced decode steps against the oracle in float64 on the same unrounded fp32
+    weights, within FP32_TOL (these models are shallower than the 12 blocks it was measured over). Measured on the
+    MI355X: at most 3.0e-7 (2.1e-7 pythia-14m, 3.0e-7 head_size 256, 2.6e-7 falcon-shaped)."""
+    cfg = _neox_cfg(kind)
+    sd = _neox_weights(cfg)
+    got = _teacher_forced(_product_step(_neox_model(cfg, sd, torch.float32)), cfg)
+    exp = _teacher_forced(_oracle_step(om.OracleGPT(cfg, sd, dtype=torch.float64)), cfg)
+    worst = 0.0
+    for i, (g, e) in enumerate(zip(got, exp)):
+        assert g.dtype == torch.float32 and g.shape == e.shape == (cfg.padded_vocab_size,)
+        err = float((g.double() - e).abs().max() / e.abs().max())
+        worst = max(worst, err)
+        assert err <= FP32_TOL, (kind, i, err)
+    print(f"{kind} fp32 vs float64 oracle: max relative error {worst:.2e}")
+
+
+@torch.inference_mode()
+def test_neox_falcon_block_bf16_matches_oracles():
+    """The falcon-shaped block in bf16 (head_size 64: the bf16 attention kernels take it): the first GQA / MQA run of
+    the NeoX block, against the bf16 and float64 oracles with the bounds of tests/parity.py."""
+    cfg = _neox_cfg("falcon")
+    sd = _neox_weights(cfg)
+    got = _teacher_forced(_product_step(_neox_model(cfg, sd, torch.bfloat16)), cfg)
+    refs = {dt: _teacher_forced(_oracle_step(o), cfg) for dt, o in _oracles(cfg, sd, "bf16").items()}
+    for i, g in enumerate(got):
+        check_step(g, refs[torch.bfloat16][i], refs[torch.float64][i], f"falcon-shaped bf16 step {i}")
+
+
+@pytest.mark.parametrize("kind,hs", [("pythia-14m", 32), ("hs256", 256)])
+@torch.inference_mode()
+def test_neox_bf16_refuses_head_sizes_without_a_kernel(kind, hs):
+    """The bf16 attention kernels exist for head_size 64 and 128 only: at 32 and 256 the product must raise an error
+    that names the head size (prefill and decode alike) and return no logits — only --precision 32-true runs these
+    geometries."""
+    cfg = _neox_cfg(kind)
+    assert cfg.head_size == hs
+    model = _neox_model(cfg, _neox_weights(cfg), torch.bfloat16)
+    toks = torch.from_numpy(synth.token_ids(NEOX_T, cfg.vocab_size, seed=4321)).long().to(DEV)
+    for t, p in ((toks, torch.arange(NEOX_T, device=DEV)), (toks[:1], torch.tensor([0], device=DEV))):
+        with pytest.raises(RuntimeError, match="head_size must be 64 or 128"):
+            model(t.view(1, -1), p)
