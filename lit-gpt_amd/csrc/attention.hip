@@ -17,8 +17,7 @@
 // the same launch; MI355X_MICROARCH.md "Valid forms" row 1), then re-arms the counter for the next launch.
 #include <cstdlib>
 
-#include "decode_ops.h"
-#include "kv8_ops.h"
+#include "attn_core.h"
 
 namespace lga {
 
@@ -65,15 +64,6 @@ __device__ __forceinline__ uint2 ld_kv8(const uint8_t* p) {
   const u32x2_t v = __builtin_nontemporal_load((const u32x2_t*)p);
   return make_uint2(v.x, v.y);
 }
-template <bool KV8>
-struct kv_regs {  // one lane's share of a K or V row in flight
-  uint4 d;
-};
-template <>
-struct kv_regs<true> {
-  uint2 d;
-  float s;
-};
 
 // FUSED (decode, T = 1): q, k, v come straight from the qkv projection row; every workgroup ropes its group's
 // q heads itself, and the workgroup whose split owns the new position p ropes k, appends k and v to the cache
@@ -138,9 +128,7 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   if (WINDOW || BATCH) q += (size_t)t * (n_head + 2 * (gridDim.y / hsplit)) * HS;  // row t of the (M, (H + 2G) hs) qkv
   if constexpr (BATCH) {
     if (active != nullptr && active[t] == 0) {  // idle row: zero y[t] (split 0), touch nothing else
-      constexpr int NQ0 = QPK * HS / 4;
-      if (split == 0 && threadIdx.x < NQ0)
-        *(uint2*)(y + ((size_t)t * n_head + (size_t)g * QPKT + hsi * QPK) * HS + threadIdx.x * 4) = make_uint2(0u, 0u);
+      attn_zero_idle<HS, QPK>(y + ((size_t)t * n_head + (size_t)g * QPKT + hsi * QPK) * HS, split);
       return;
     }
     // sequence t's slot: KV8 codes are bytes behind the uint16_t pointers, bf16 rows are elements
@@ -151,13 +139,9 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
       vsc += (size_t)t * scale_slot_stride;
     }
   }
-  const int L = (int)min(p + 1, (long)max_seq);  // keys 0..p (never past the cache)
-  const int chunk = (L + n_splits - 1) / n_splits;
-  const int k_lo = split * chunk;
-  const int k_hi = min(k_lo + chunk, L);
+  const attn_range sp = attn_split_range<FUSED>(p, max_seq, n_splits, split);
+  const int k_lo = sp.k_lo, k_end = sp.k_end;
   LGA_TRACE(1);
-  const bool owns_new = FUSED && p < max_seq && k_lo <= p && p < k_hi;
-  const int k_end = FUSED ? min(k_hi, (int)p) : k_hi;  // fused: key p is scored from registers below
   const float* cr = nullptr;
   const float* sr = nullptr;
   if (FUSED) {
@@ -172,7 +156,7 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   const uint8_t* vbase8 = (const uint8_t*)vc + (size_t)g * max_seq * HS + sub * 8;
   const float* ksg = KV8 ? ksc + (size_t)g * max_seq : nullptr;
   const float* vsg = KV8 ? vsc + (size_t)g * max_seq : nullptr;
-  // clamped duplicate rows (past k_end) are masked in consume() and hit in cache
+  // clamped duplicate rows (past k_end) are masked in attn_step() and hit in cache
   auto fetch = [&](kv_regs<KV8> (&kv)[UNR], kv_regs<KV8> (&vv)[UNR], int j0) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
@@ -208,10 +192,7 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
       sn[i] = sr[i];
     }
   }
-  // q stays packed bf16 (as the reference's bf16 q): scores are v_dot2_f32_bf16 chains — two exact bf16 products
-  // per instruction into an fp32 accumulator, half the VALU of unpack + fma. Interleaved A/B (tools/attn_ab.py,
-  // round 5) at p = 32066, 32 splits: Mixtral 34.8 -> 33.8 us, its TP = 2 rank 24.8 -> 23.5; Llama-2-7B neutral
-  uint4 qp[QPK];
+  uint4 qp[QPK];  // q stays packed bf16 (attn_dot8)
 #pragma unroll
   for (int h = 0; h < QPK; ++h) qp[h] = FUSED ? rope8(qraw[h], cs, sn, sub) : qraw[h];
   // the online softmax runs in log2 units (as the prefill's flash attention): scores scaled by scale * log2(e), every
@@ -219,23 +200,12 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   // VALU-bound (tools/attn_pmc.py: Mixtral at p = 32066, the waves VALU-active 40 % of their cycles, 2 per SIMD);
   // the partials' m is in log2 units too (only this kernel's combine reads it)
   const float sl2 = scale * 1.4426950408889634f;
-  auto dot8 = [](const uint4 a, const uint4 b) {
-    typedef short s2 __attribute__((ext_vector_type(2)));
-    float d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.x), __builtin_bit_cast(s2, b.x), 0.0f, false);
-    d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.y), __builtin_bit_cast(s2, b.y), d, false);
-    d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.z), __builtin_bit_cast(s2, b.z), d, false);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.w), __builtin_bit_cast(s2, b.w), d, false);
-  };
   // the first K/V batch AFTER the RoPE: issued beside q (ahead of the RoPE's wait) every split's first loads leave
   // in one burst at kernel start, measured 0.25-0.3 us slower per launch (tools/attn_ab.py, round 5)
   __builtin_amdgcn_sched_barrier(0);
   kv_regs<KV8> ka[UNR], va[UNR], kb[UNR], vb[UNR];
   if (PIPE) fetch(ka, va, j_first);
   LGA_TRACE(2);
-  // m starts at a finite floor, not -inf: every row group runs the split's step count, so one whose keys are all
-  // past k_end sees only masked (-inf) scores, and exp(floor - floor) = 1 keeps its (l, o) = 0 instead of NaN; a
-  // real first score s gives exp(kMFloor - s) = 0 exactly as exp(-inf) did
-  constexpr float kMFloor = -1e30f;
   float m[QPK], l[QPK], o[QPK][8];
 #pragma unroll
   for (int h = 0; h < QPK; ++h) {
@@ -244,42 +214,8 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
 #pragma unroll
     for (int i = 0; i < 8; ++i) o[h][i] = 0.0f;
   }
-  // one step = UNR keys per row group: scores, online-softmax rescale, P.V (masked keys score -inf)
   auto consume = [&](const kv_regs<KV8> (&kv)[UNR], const kv_regs<KV8> (&vv)[UNR], int j0) {
-#pragma unroll
-    for (int h = 0; h < QPK; ++h) {
-      float s[UNR];
-      float mx = m[h];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        float sd;  // whole row group active: DPP inside it
-        if constexpr (KV8) sd = row_group_sum<LPR>(dot8(qp[h], kv8_bf16x8(kv[u].d))) * (kv[u].s * sl2);
-        else sd = row_group_sum<LPR>(dot8(qp[h], kv[u].d)) * sl2;
-        s[u] = (j0 + u * RG < k_end) ? sd : -INFINITY;
-        mx = fmaxf(mx, s[u]);
-      }
-      const float c = __builtin_amdgcn_exp2f(m[h] - mx);  // m = kMFloor (first step) -> 0
-      l[h] *= c;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[h][i] *= c;
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const float e = __builtin_amdgcn_exp2f(s[u] - mx);  // masked keys: exp(-inf) = 0
-        l[h] += e;
-        float vf[8];
-        if constexpr (KV8) {
-          kv8_f32x8(vv[u].d, vf);
-          const float ev = e * vv[u].s;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) o[h][i] = fmaf(ev, vf[i], o[h][i]);
-        } else {
-          unpack8(vv[u].d, vf);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) o[h][i] = fmaf(e, vf[i], o[h][i]);
-        }
-      }
-      m[h] = mx;
-    }
+    attn_step<LPR, QPK, UNR, RG, KV8>(m, l, o, qp, kv, vv, j0, k_end, sl2);
   };
   if (PIPE) {
     // software pipeline: step i + 1's 2*UNR loads are issued before step i's math, so every row group keeps 2-4
@@ -302,7 +238,7 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
     }
   }
   LGA_TRACE(3);
-  if (FUSED && owns_new && rg == 0) {  // the new key/value: rope k, append both to the cache, score from registers
+  if (FUSED && sp.owns_new && rg == 0) {  // the new key/value: rope k, append both to the cache, score from registers
     const uint16_t* kvrow = q + ((size_t)g * (QPKT + 2) + QPKT) * HS + sub * 8;
     uint4 kr = rope8(*(const uint4*)kvrow, cs, sn, sub);
     const uint4 vr = *(const uint4*)(kvrow + HS);
@@ -329,50 +265,15 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
       }
       unpack8(vr, vf);
     }
-#pragma unroll
-    for (int h = 0; h < QPK; ++h) {
-      float s;
-      if constexpr (KV8) s = row_group_sum<LPR>(dot8(qp[h], kr)) * (ksn * sl2);
-      else s = row_group_sum<LPR>(dot8(qp[h], kr)) * sl2;
-      const float mx = fmaxf(m[h], s);
-      const float c = __builtin_amdgcn_exp2f(m[h] - mx);
-      const float e = __builtin_amdgcn_exp2f(s - mx);
-      l[h] = l[h] * c + e;
-      const float ev = KV8 ? e * vsn : e;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[h][i] = fmaf(ev, vf[i], o[h][i] * c);
-      m[h] = mx;
-    }
+    attn_new_key<LPR, QPK, KV8>(m, l, o, qp, kr, vf, ksn, vsn, sl2);
   }
   // merge the RGW row groups of this wave (lanes differing in the bits above log2(LPR))
 #pragma unroll
-  for (int off = LPR; off < 64; off <<= 1) {
-#pragma unroll
-    for (int h = 0; h < QPK; ++h) {
-      const float mo = __shfl_xor(m[h], off), lo = __shfl_xor(l[h], off);
-      const float mn = fmaxf(m[h], mo);
-      const float ca = __builtin_amdgcn_exp2f(m[h] - mn);  // m >= kMFloor: finite, never exp(-inf - -inf)
-      const float cb = __builtin_amdgcn_exp2f(mo - mn);
-      l[h] = l[h] * ca + lo * cb;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[h][i] = o[h][i] * ca + __shfl_xor(o[h][i], off) * cb;
-      m[h] = mn;
-    }
-  }
+  for (int off = LPR; off < 64; off <<= 1) attn_wave_merge<QPK>(m, l, o, off);
   __shared__ float sm[NW][QPK], sl[NW][QPK];
   __shared__ __attribute__((aligned(16))) float so[NW][QPK][HS];
   __shared__ unsigned s_ticket;
-  if (lane < LPR) {
-#pragma unroll
-    for (int h = 0; h < QPK; ++h) {
-      if (lane == 0) {
-        sm[wave][h] = m[h];
-        sl[wave][h] = l[h];
-      }
-      *(float4*)&so[wave][h][sub * 8] = make_float4(o[h][0], o[h][1], o[h][2], o[h][3]);
-      *(float4*)&so[wave][h][sub * 8 + 4] = make_float4(o[h][4], o[h][5], o[h][6], o[h][7]);
-    }
-  }
+  attn_stash<LPR>(sm[wave], sl[wave], so[wave], m, l, o, lane);
   __syncthreads();
   // block merge: a thread owns 4 consecutive output columns (h, 4 dq .. 4 dq + 3) of one head of the slice
   constexpr int NQ = QPK * HS / 4;
@@ -380,46 +281,22 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   const bool has_item = threadIdx.x < NQ;
   const int hq = threadIdx.x / (HS / 4), dq = threadIdx.x % (HS / 4);
   float bm = -INFINITY, bl = 0.0f, bo[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (has_item) {
-#pragma unroll
-    for (int w = 0; w < NW; ++w) bm = fmaxf(bm, sm[w][hq]);
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float c = __builtin_amdgcn_exp2f(sm[w][hq] - bm);
-      bl += sl[w][hq] * c;
-      const float4 ov = *(const float4*)&so[w][hq][dq * 4];
-      bo[0] += ov.x * c;
-      bo[1] += ov.y * c;
-      bo[2] += ov.z * c;
-      bo[3] += ov.w * c;
-    }
-  }
+  if (has_item) attn_block_merge(sm, sl, so, hq, dq, bm, bl, bo);
   const size_t row0 = (size_t)t * n_head + (size_t)g * QPKT + hsi * QPK;  // first head row of this slice
   if (n_splits == 1) {
-    if (has_item) {
-      uint16_t* yr = y + (row0 + hq) * HS + dq * 4;
-      *(uint2*)yr = make_uint2(pack2(bo[0] / bl, bo[1] / bl), pack2(bo[2] / bl, bo[3] / bl));
-    }
+    if (has_item) attn_store_quad(y + (row0 + hq) * HS + dq * 4, bo, bl);
     return;
   }
   LGA_TRACE(4);
   // ---- publish (m, l, o), then the last-arriving split of this (t, group) merges all splits (MI355X_MICROARCH.md
   // "Valid forms" row 1: 16-B sc1 stores, every storing wave drains, a workgroup barrier, one lane's agent-scope
-  // add; the last arriver's loads are sc1 too). Per (head row, split): {m, l, 0, 0, o[HS]} fp32 ----
+  // add; the last arriver's loads are sc1 too) ----
   // SOLO: every output quad sits in wave 0 (QPK * HS / 4 <= 64), so wave 0 alone stores, drains, counts and, when
   // last, combines: the same row-1 form with one storing wave, no workgroup barrier or LDS ticket on the tail
   constexpr bool SOLO = LGA_ATTN_SOLO && NQ <= 64;
   if (SOLO && wave != 0) return;
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(ws + row0 * n_splits * (HS + 4)), (short)0, QPK * n_splits * (HS + 4) * 4, 0x00020000);
-  if (has_item) {
-    const unsigned off = (unsigned)((hq * n_splits + split) * (HS + 4)) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, make_float4(bo[0], bo[1], bo[2], bo[3])), wrs,
-                                           off + 16 + dq * 16, 0, 16);
-    if (dq == 0)
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, make_float4(bm, bl, 0.0f, 0.0f)), wrs, off,
-                                             0, 16);
-  }
+  const __amdgpu_buffer_rsrc_t wrs = attn_ws_rsrc<HS, QPK>(ws, row0, n_splits);
+  if (has_item) attn_publish<HS>(wrs, hq, dq, n_splits, split, bm, bl, bo);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   unsigned* ctr = cnt + ((size_t)t * gridDim.y + gy) * kCounterStride;
   unsigned ticket;
@@ -435,45 +312,7 @@ __device__ __forceinline__ void attn_body(const uint16_t* __restrict__ q, uint16
   }
   LGA_TRACE(5);
   if (ticket != (unsigned)(n_splits - 1)) return;
-  // one output column quad per thread, 8 splits per round with every load of the round in flight at once and an
-  // online rescale across rounds. Split 0 always holds key 0, so the running max is finite after round 0; empty
-  // splits carry m = kMFloor, l = 0, o = 0 and clamped out-of-range slots are forced to m = -inf: both weigh 0.
-  if (has_item) {
-    const unsigned hoff = (unsigned)(hq * n_splits * (HS + 4)) * 4;
-    float mx = -INFINITY, lt = 0.0f, ot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int s0 = 0; s0 < n_splits; s0 += 8) {
-      float4 ml[8], o4[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const unsigned off = hoff + (unsigned)(min(s0 + u, n_splits - 1) * (HS + 4)) * 4;
-        ml[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrs, off, 0, 16));
-        o4[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrs, off + 16 + dq * 16, 0, 16));
-      }
-      float nm = mx;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        if (s0 + u >= n_splits) ml[u].x = -INFINITY;
-        nm = fmaxf(nm, ml[u].x);
-      }
-      const float c = __builtin_amdgcn_exp2f(mx - nm);  // round 0: exp(-inf) = 0
-      lt *= c;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) ot[i] *= c;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const float e = __builtin_amdgcn_exp2f(ml[u].x - nm);
-        lt = fmaf(ml[u].y, e, lt);
-        ot[0] = fmaf(o4[u].x, e, ot[0]);
-        ot[1] = fmaf(o4[u].y, e, ot[1]);
-        ot[2] = fmaf(o4[u].z, e, ot[2]);
-        ot[3] = fmaf(o4[u].w, e, ot[3]);
-      }
-      mx = nm;
-    }
-    uint16_t* yr = y + (row0 + hq) * HS + dq * 4;
-    const uint2 yv = make_uint2(pack2(ot[0] / lt, ot[1] / lt), pack2(ot[2] / lt, ot[3] / lt));
-    *(uint2*)yr = yv;
-  }
+  if (has_item) attn_combine<HS>(wrs, hq, dq, n_splits, y, row0 + hq);  // one quad per thread
   if (threadIdx.x == 0) __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
   LGA_TRACE(6);
 }
@@ -521,12 +360,10 @@ __global__ void __launch_bounds__(NW * 64) attn_kernel_kv8(const uint16_t* __res
 // pipelined item sequence: item n sits in ka / va (n even) or kb / vb (n odd) and item n + 1's loads are issued
 // ahead of item n's math, across the change of row too. No state passes between workgroups. Idle rows (active[b] ==
 // 0, or b >= B in the last set) are skipped; a set with no active row returns as the batch form's idle row does.
-// Every multiply-add below is written as the ONE form hipcc gives attn_body in all its fused instantiations (fma, or
-// mul_rn / add_rn; read off their ISA). Left to -ffp-contract, this body's other shape had two of them fused
-// differently (the wave merge's l, the block merge's bl): one ulp apart, one output element in thousands.
-// attn_body's own forms stay the compiler's choice: a hipcc that fuses attn_body differently parts the two kernels, and
-// only the bit-identity tests on the GPU (tests/test_gpu_shared_attention.py) show it; the forms here then follow
-// attn_body's new ISA (or attn_body's merges get written out the same way).
+// The arithmetic of a pair is attn_body's because it is the same code: both kernels call the one softmax core
+// (attn_core.h), whose every multiply-add is an explicit fma / mul_rn / add_rn, so no compiler choice can part them.
+// (Left to -ffp-contract, this body's other shape once had two of them fused differently — the wave merge's l, the
+// block merge's bl: one ulp apart, one output element in thousands.) tests/test_gpu_shared_attention.py holds the bits.
 template <int HS, int QPK, int UNR, int NW, int R>
 __global__ void __launch_bounds__(NW * 64)
     attn_shared_kernel(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
@@ -556,26 +393,20 @@ __global__ void __launch_bounds__(NW * 64)
     if (active == nullptr || active[b] != 0) {
       am |= 1u << r;
     } else {  // idle row: zero y[b] (split 0), touch nothing else
-      constexpr int NQ0 = QPK * HS / 4;
-      if (split == 0 && threadIdx.x < NQ0)
-        *(uint2*)(y + ((size_t)b * n_head + (size_t)g * QPKT + hsi * QPK) * HS + threadIdx.x * 4) = make_uint2(0u, 0u);
+      attn_zero_idle<HS, QPK>(y + ((size_t)b * n_head + (size_t)g * QPKT + hsi * QPK) * HS, split);
     }
   }
   if (am == 0) return;
-  const int L = (int)min(p + 1, (long)max_seq);  // keys 0..p (never past the cache)
-  const int chunk = (L + n_splits - 1) / n_splits;
-  const int k_lo = split * chunk;
-  const int k_hi = min(k_lo + chunk, L);
-  const bool owns_new = p < max_seq && k_lo <= p && p < k_hi;
-  const int k_end = min(k_hi, (int)min(p, (long)max_seq));  // key p is scored from registers below
-  const int P = (int)min(pfx, (long)max_seq);               // (keys at or past max_seq are never loaded)
+  const attn_range sp = attn_split_range<true>(p, max_seq, n_splits, split);  // (key p is scored from registers)
+  const int k_lo = sp.k_lo, k_end = sp.k_end;
+  const int P = (int)min(pfx, (long)max_seq);  // (keys at or past max_seq are never loaded)
   const long rp = min(max(p, 0L), (long)rope_rows - 1);
   const float* cr = cos + (size_t)rp * HS + sub * 8;
   const float* sr = sin + (size_t)rp * HS + sub * 8;
   const uint16_t* kbase = kc + (size_t)g * max_seq * HS + sub * 8;  // slot 0
   const uint16_t* vbase = vc + (size_t)g * max_seq * HS + sub * 8;
   // one item's loads: key j comes from slot 0 below P, else from the slot `own` elements on (a shared step passes 0);
-  // clamped duplicate rows (past k_end) are masked in consume() and hit in cache
+  // clamped duplicate rows (past k_end) are masked in attn_step() and hit in cache
   auto fetch = [&](kv_regs<false> (&kv)[UNR], kv_regs<false> (&vv)[UNR], int j0, size_t own) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
@@ -609,13 +440,6 @@ __global__ void __launch_bounds__(NW * 64)
 #pragma unroll
     for (int h = 0; h < QPK; ++h) qp[r][h] = rope8(qraw[r][h], cs, sn, sub);
   const float sl2 = scale * 1.4426950408889634f;
-  auto dot8 = [](const uint4 a, const uint4 b) {
-    typedef short s2 __attribute__((ext_vector_type(2)));
-    float d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.x), __builtin_bit_cast(s2, b.x), 0.0f, false);
-    d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.y), __builtin_bit_cast(s2, b.y), d, false);
-    d = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.z), __builtin_bit_cast(s2, b.z), d, false);
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(s2, a.w), __builtin_bit_cast(s2, b.w), d, false);
-  };
   // the item sequence: ns shared steps, then the nown own steps of every active row
   const int stp = RG * UNR;
   const int nst = k_end > k_lo ? (k_end - k_lo + stp - 1) / stp : 0;
@@ -627,7 +451,6 @@ __global__ void __launch_bounds__(NW * 64)
   kv_regs<false> ka[UNR], va[UNR], kb[UNR], vb[UNR];
   if (ns > 0) fetch(ka, va, j_first, 0);
   else if (nown > 0) fetch(ka, va, j_first, own_of(r_first));
-  constexpr float kMFloor = -1e30f;
   float m[R][QPK], l[R][QPK], o[R][QPK][8];
 #pragma unroll
   for (int r = 0; r < R; ++r)
@@ -638,33 +461,10 @@ __global__ void __launch_bounds__(NW * 64)
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[r][h][i] = 0.0f;
     }
-  // one step of one row: attn_body's consume() on that row's QPK states
-  auto consume = [&](float (&mr)[QPK], float (&lr)[QPK], float (&orr)[QPK][8], const uint4 (&qr)[QPK],
-                     const kv_regs<false> (&kv)[UNR], const kv_regs<false> (&vv)[UNR], int j0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int h = 0; h < QPK; ++h) {
-      float s[UNR];
-      float mx = mr[h];
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const float sd = mul_rn(row_group_sum<LPR>(dot8(qr[h], kv[u].d)), sl2);
-        s[u] = (j0 + u * RG < k_end) ? sd : -INFINITY;
-        mx = fmaxf(mx, s[u]);
-      }
-      const float c = __builtin_amdgcn_exp2f(mr[h] - mx);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) orr[h][i] = mul_rn(orr[h][i], c);
-#pragma unroll
-      for (int u = 0; u < UNR; ++u) {
-        const float e = __builtin_amdgcn_exp2f(s[u] - mx);
-        lr[h] = u == 0 ? __builtin_fmaf(lr[h], c, e) : add_rn(lr[h], e);
-        float vf[8];
-        unpack8(vv[u].d, vf);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) orr[h][i] = __builtin_fmaf(e, vf[i], orr[h][i]);
-      }
-      mr[h] = mx;
-    }
+  // one step of one row: attn_body's, on that row's QPK states
+  auto consume = [&](int r, const kv_regs<false> (&kv)[UNR], const kv_regs<false> (&vv)[UNR], int j0)
+                     __attribute__((always_inline)) {
+    attn_step<LPR, QPK, UNR, RG, false>(m[r], l[r], o[r], qp[r], kv, vv, j0, k_end, sl2);
   };
   int n = 0;  // items consumed so far
   // item n: issue the next item's loads (if any) into the other buffer, then the math `use` on item n's
@@ -685,7 +485,7 @@ __global__ void __launch_bounds__(NW * 64)
          [&](const kv_regs<false>(&kv)[UNR], const kv_regs<false>(&vv)[UNR]) __attribute__((always_inline)) {
 #pragma unroll
            for (int r = 0; r < R; ++r)
-             if (am >> r & 1) consume(m[r], l[r], o[r], qp[r], kv, vv, j0);
+             if (am >> r & 1) consume(r, kv, vv, j0);
          });
   }
 #pragma unroll
@@ -698,11 +498,11 @@ __global__ void __launch_bounds__(NW * 64)
       const int j0 = j_first + i * stp;
       item(more || r_next >= 0, j_first + (more ? i + 1 : ns) * stp, own_of(more ? r : max(r_next, 0)),
            [&](const kv_regs<false>(&kv)[UNR], const kv_regs<false>(&vv)[UNR]) __attribute__((always_inline)) {
-             consume(m[r], l[r], o[r], qp[r], kv, vv, j0);
+             consume(r, kv, vv, j0);
            });
     }
   }
-  if (owns_new && rg == 0) {  // every row's new key/value: rope k, append both to slot b, score from registers
+  if (sp.owns_new && rg == 0) {  // every row's new key/value: rope k, append both to slot b, score from registers
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (!(am >> r & 1)) continue;
@@ -715,57 +515,23 @@ __global__ void __launch_bounds__(NW * 64)
       }
       float vf[8];
       unpack8(vr, vf);
-#pragma unroll
-      for (int h = 0; h < QPK; ++h) {
-        const float sd = row_group_sum<LPR>(dot8(qp[r][h], kr));
-        const float mx = fmaxf(m[r][h], mul_rn(sd, sl2));
-        const float c = __builtin_amdgcn_exp2f(m[r][h] - mx);
-        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(sd, sl2, -mx));
-        l[r][h] = __builtin_fmaf(l[r][h], c, e);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[r][h][i] = __builtin_fmaf(e, vf[i], mul_rn(o[r][h][i], c));
-        m[r][h] = mx;
-      }
+      attn_new_key<LPR, QPK, false>(m[r], l[r], o[r], qp[r], kr, vf, 1.0f, 1.0f, sl2);
     }
   }
   // merge the RGW row groups of this wave, pair by pair
 #pragma unroll
   for (int off = LPR; off < 64; off <<= 1) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (!(am >> r & 1)) continue;
-#pragma unroll
-      for (int h = 0; h < QPK; ++h) {
-        const float mo = __shfl_xor(m[r][h], off), lo = __shfl_xor(l[r][h], off);
-        const float mn = fmaxf(m[r][h], mo);
-        const float ca = __builtin_amdgcn_exp2f(m[r][h] - mn);
-        const float cb = __builtin_amdgcn_exp2f(mo - mn);
-        l[r][h] = __builtin_fmaf(l[r][h], ca, mul_rn(lo, cb));
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          o[r][h][i] = __builtin_fmaf(o[r][h][i], ca, mul_rn(__shfl_xor(o[r][h][i], off), cb));
-        m[r][h] = mn;
-      }
-    }
+    for (int r = 0; r < R; ++r)
+      if (am >> r & 1) attn_wave_merge<QPK>(m[r], l[r], o[r], off);
   }
   __shared__ float sm[NW][NP], sl[NW][NP];
   __shared__ __attribute__((aligned(16))) float so[NW][NP][HS];
   __shared__ unsigned s_ticket[R];
-  if (lane < LPR) {
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (!(am >> r & 1)) continue;
-#pragma unroll
-      for (int h = 0; h < QPK; ++h) {
-        if (lane == 0) {
-          sm[wave][r * QPK + h] = m[r][h];
-          sl[wave][r * QPK + h] = l[r][h];
-        }
-        *(float4*)&so[wave][r * QPK + h][sub * 8] = make_float4(o[r][h][0], o[r][h][1], o[r][h][2], o[r][h][3]);
-        *(float4*)&so[wave][r * QPK + h][sub * 8 + 4] = make_float4(o[r][h][4], o[r][h][5], o[r][h][6], o[r][h][7]);
-      }
-    }
-  }
+  for (int r = 0; r < R; ++r)
+    if (am >> r & 1)
+      attn_stash<LPR>(&sm[wave][r * QPK], &sl[wave][r * QPK], &so[wave][r * QPK], m[r], l[r], o[r], lane);
   __syncthreads();
   // block merge per row: a thread owns 4 consecutive output columns of one head of the slice, as in attn_body
   constexpr int NQ = QPK * HS / 4;
@@ -775,40 +541,14 @@ __global__ void __launch_bounds__(NW * 64)
   const bool has_item = threadIdx.x < NQ;
   const int hq = threadIdx.x / (HS / 4), dq = threadIdx.x % (HS / 4);
   const size_t slice0 = (size_t)g * QPKT + hsi * QPK;  // first head of this slice
-  auto ws_rsrc = [&](int r) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(ws + ((size_t)(b0 + r) * n_head + slice0) * n_splits * (HS + 4)),
-                                             (short)0, QPK * n_splits * (HS + 4) * 4, 0x00020000);
-  };
+  auto ws_rsrc = [&](int r) { return attn_ws_rsrc<HS, QPK>(ws, (size_t)(b0 + r) * n_head + slice0, n_splits); };
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    if (!(am >> r & 1)) continue;
+    if (!(am >> r & 1) || !has_item) continue;
     float bm = -INFINITY, bl = 0.0f, bo[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (has_item) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) bm = fmaxf(bm, sm[w][r * QPK + hq]);
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        const float c = __builtin_amdgcn_exp2f(sm[w][r * QPK + hq] - bm);
-        bl = add_rn(bl, mul_rn(sl[w][r * QPK + hq], c));
-        const float4 ov = *(const float4*)&so[w][r * QPK + hq][dq * 4];
-        bo[0] = __builtin_fmaf(ov.x, c, bo[0]);
-        bo[1] = __builtin_fmaf(ov.y, c, bo[1]);
-        bo[2] = __builtin_fmaf(ov.z, c, bo[2]);
-        bo[3] = __builtin_fmaf(ov.w, c, bo[3]);
-      }
-      if (n_splits == 1) {
-        uint16_t* yr = y + ((size_t)(b0 + r) * n_head + slice0 + hq) * HS + dq * 4;
-        *(uint2*)yr = make_uint2(pack2(bo[0] / bl, bo[1] / bl), pack2(bo[2] / bl, bo[3] / bl));
-      } else {  // publish (m, l, o) of this (row, split): attn_body's layout, row t = b
-        const __amdgpu_buffer_rsrc_t wrs = ws_rsrc(r);
-        const unsigned off = (unsigned)((hq * n_splits + split) * (HS + 4)) * 4;
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, make_float4(bo[0], bo[1], bo[2], bo[3])),
-                                               wrs, off + 16 + dq * 16, 0, 16);
-        if (dq == 0)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, make_float4(bm, bl, 0.0f, 0.0f)), wrs,
-                                                 off, 0, 16);
-      }
-    }
+    attn_block_merge(sm, sl, so, r * QPK + hq, dq, bm, bl, bo);
+    if (n_splits == 1) attn_store_quad(y + ((size_t)(b0 + r) * n_head + slice0 + hq) * HS + dq * 4, bo, bl);
+    else attn_publish<HS>(ws_rsrc(r), hq, dq, n_splits, split, bm, bl, bo);  // attn_body's layout, row t = b
   }
   if (n_splits == 1) return;
   // one drain for all rows' partials, then the rows' arrival counters side by side (thread r counts for row r): the
@@ -828,42 +568,7 @@ __global__ void __launch_bounds__(NW * 64)
     if (!(am >> r & 1)) continue;
     const unsigned ticket = SOLO ? (unsigned)__builtin_amdgcn_readlane((int)tk, r) : s_ticket[r];
     if (ticket != (unsigned)(n_splits - 1)) continue;
-    if (has_item) {  // attn_body's combine
-      const __amdgpu_buffer_rsrc_t wrs = ws_rsrc(r);
-      const unsigned hoff = (unsigned)(hq * n_splits * (HS + 4)) * 4;
-      float mx = -INFINITY, lt = 0.0f, ot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      for (int s0 = 0; s0 < n_splits; s0 += 8) {
-        float4 ml[8], o4[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const unsigned off = hoff + (unsigned)(min(s0 + u, n_splits - 1) * (HS + 4)) * 4;
-          ml[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrs, off, 0, 16));
-          o4[u] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrs, off + 16 + dq * 16, 0, 16));
-        }
-        float nm = mx;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          if (s0 + u >= n_splits) ml[u].x = -INFINITY;
-          nm = fmaxf(nm, ml[u].x);
-        }
-        const float c = __builtin_amdgcn_exp2f(mx - nm);
-        lt = mul_rn(lt, c);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ot[i] = mul_rn(ot[i], c);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const float e = __builtin_amdgcn_exp2f(ml[u].x - nm);
-          lt = fmaf(ml[u].y, e, lt);
-          ot[0] = fmaf(o4[u].x, e, ot[0]);
-          ot[1] = fmaf(o4[u].y, e, ot[1]);
-          ot[2] = fmaf(o4[u].z, e, ot[2]);
-          ot[3] = fmaf(o4[u].w, e, ot[3]);
-        }
-        mx = nm;
-      }
-      uint16_t* yr = y + ((size_t)(b0 + r) * n_head + slice0 + hq) * HS + dq * 4;
-      *(uint2*)yr = make_uint2(pack2(ot[0] / lt, ot[1] / lt), pack2(ot[2] / lt, ot[3] / lt));
-    }
+    if (has_item) attn_combine<HS>(ws_rsrc(r), hq, dq, n_splits, y, (size_t)(b0 + r) * n_head + slice0 + hq);
     if (threadIdx.x == 0) __hip_atomic_store(ctr_of(r), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
   }
 }
