@@ -319,6 +319,25 @@ int lga_kv8_dequantize(const void* k_codes, const void* v_codes, const float* k_
 int lga_spec_accept(const void* logits, int M, int n, const int32_t* window, int32_t* out, int32_t* token_inout,
                     int64_t* pos_inout, lga_stream_t stream);
 
+/* -- LLaMA-Adapter v1 (lit_gpt/adapter.py CausalSelfAttention.scaled_dot_product_attention) ------------------------
+ * The gated prefix-attention term, added in place to the T rows of an attention result y (T, H*hs) bf16:
+ *   y[t, h] = bf16(y[t, h] + bf16(g_h * ay)),  ay = bf16(softmax(scale * q^ ak_g^T) av_g),  g = h / (H / G).
+ * qkv (T, (H + 2G) * hs) is the fused projection in the per-group layout of lga_rope_kv_append, q NOT roped: the
+ * kernel computes q^ = bf16(rope(q)) itself, with lga_rope_kv_append's arithmetic, from row p_t of the cos / sin
+ * tables (rope_rows, rope_n_elem) fp32. ak / av (G, aT, hs) bf16 are the k / v slices of attn.attn(adapter_wte.weight),
+ * un-expanded, never roped; every one of the aT keys is visible to every query (no mask). gating (H) bf16. Scores and
+ * the softmax are fp32. The positions are read on the device (a captured launch follows a later write):
+ *   pos_mode 0: p_t = pos[t] (T int64);  1: p_t = pos[0] + t (the verify window);  2: p_t = pos[0] (samples of one
+ *   prompt in lock step).
+ * active (T) int32 or NULL: a row with active[t] == 0 is skipped before anything that depends on its position is
+ * loaded, and so is a row whose position is outside [0, rope_rows): y[t] keeps its bits. A row's result depends on no
+ * other row, on T or on the launch grid. No workspace. bf16 only; head_size % 8 == 0, head_size <= 256; rope_n_elem
+ * even, <= head_size; H % G == 0; 1 <= aT <= 64; ak 16-B aligned. */
+int lga_adapter_attention(const void* qkv, const void* ak, const void* av, const void* gating, const float* cos,
+                          const float* sin, int rope_rows, const int64_t* pos, int pos_mode, const int32_t* active,
+                          void* y, int T, int n_head, int n_query_groups, int head_size, int rope_n_elem, int aT,
+                          float scale, lga_stream_t stream);
+
 /* -- sparse MoE (LLaMAMoE.forward, lit_gpt/model.py:727-743; Mixtral) ------------------------------------------
  * lga_moe_route: per token row of router logits [T][n_expert] bf16 -> expert_ids [T][k] int32 and probs [T][k]
  * bf16 = topk(router, k) with the CPU torch.topk order on ties (model.py:737) and

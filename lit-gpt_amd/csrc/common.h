@@ -100,6 +100,7 @@ int preload_norm_rope();
 int preload_sample();
 int preload_gemv();
 int preload_moe();
+int preload_adapter();
 
 }  // namespace lga
 

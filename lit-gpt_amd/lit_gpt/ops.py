@@ -90,6 +90,7 @@ SIGNATURES = {
     "lga_kv8_rope_append": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "lga_kv8_dequantize": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_spec_accept": [_P, _I, _I, _P, _P, _P, _P, _P],
+    "lga_adapter_attention": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "lga_argmax": [_P, _I, _P, _P, _P, _P],
     "lga_q4_gemv_argmax_work_bytes": [_I, _I],
     "lga_q4_gemv_argmax_embed": [_P, _P, _P, _P, _F, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P],
@@ -850,6 +851,47 @@ def attention_decode_batch_kv8(qkv, cache, pos, cos, sin, n_head, n_query_groups
     bit-identical to ``attention_decode_fused_kv8`` on that row and slot with the same ``n_splits``."""
     return _attention_decode("batch", qkv, tuple(cache), pos, pos, cos, sin, n_head, n_query_groups, head_size,
                              rope_n_elem, scale, n_splits, workspace, out, active)
+
+
+ADAPTER_MAX_KEYS = 64  # adapter_prompt_length of one lga_adapter_attention launch (a lane per key)
+ADAPTER_MAX_HEAD_SIZE = 256
+ADAPTER_POS_MODES = {"rows": 0, "window": 1, "one": 2}
+
+
+def adapter_attention(y, qkv, ak, av, gating, pos, cos, sin, n_head, n_query_groups, head_size, rope_n_elem, scale, *,
+                      pos_mode="rows", active=None):
+    """LLaMA-Adapter v1's gated prefix-attention term, in place on ``y`` (T, H * hs) bf16: y[t, h] = bf16(y[t, h] +
+    bf16(g_h * bf16(softmax(scale * rope(q[t, h]) ak^T) av))) over the aT keys of ``ak`` / ``av`` (G, aT, hs) —
+    one ``lga_adapter_attention`` launch (include/litgpt_amd.h states the rounding points). ``qkv`` (T, (H + 2G) * hs)
+    is the fused projection, q un-roped; ``cos`` / ``sin`` the fp32 tables; ``pos`` int64 on the device: ``pos_mode``
+    "rows" one position per row (T,), "window" row t at pos[0] + t, "one" every row at pos[0]. ``active`` (T,) int32:
+    rows flagged 0 keep their bits. Returns ``y``."""
+    H, G, hs = n_head, n_query_groups, head_size
+    if qkv.dim() != 2 or qkv.shape[1] != (H + 2 * G) * hs:
+        raise ValueError(f"adapter_attention: qkv must be (T, (H + 2G) * hs), got {tuple(qkv.shape)}")
+    T = qkv.shape[0]
+    if y.numel() != T * H * hs:
+        raise ValueError(f"adapter_attention: y must hold (T, H * hs) = ({T}, {H * hs}) values")
+    if ak.dim() != 3 or ak.shape[0] != G or ak.shape[2] != hs or av.shape != ak.shape:
+        raise ValueError(f"adapter_attention: ak and av must be (G, aT, hs) = ({G}, aT, {hs}), got {tuple(ak.shape)} "
+                         f"and {tuple(av.shape)}")
+    if gating.numel() != H:
+        raise ValueError(f"adapter_attention: gating must hold one factor per head ({H})")
+    if pos_mode not in ADAPTER_POS_MODES:
+        raise ValueError(f"adapter_attention: pos_mode must be one of {sorted(ADAPTER_POS_MODES)}")
+    if pos.numel() != (T if pos_mode == "rows" else 1):
+        raise ValueError(f"adapter_attention: pos_mode {pos_mode!r} takes {T if pos_mode == 'rows' else 1} "
+                         f"position(s), got {tuple(pos.shape)}")
+    if active is not None and active.numel() != T:
+        raise ValueError(f"adapter_attention: active must hold {T} int32 flags")
+    if cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != rope_n_elem:
+        raise ValueError(f"adapter_attention: cos / sin must be (rows, rope_n_elem = {rope_n_elem}) tables")
+    _check(load_library().lga_adapter_attention(
+        _dev(qkv, "qkv", torch.bfloat16), _dev(ak, "ak", torch.bfloat16), _dev(av, "av", torch.bfloat16),
+        _dev(gating, "gating", torch.bfloat16), _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32),
+        cos.shape[0], _dev(pos, "pos", torch.int64), ADAPTER_POS_MODES[pos_mode], _opt(active, "active", torch.int32),
+        _dev(y, "y", torch.bfloat16), T, H, G, hs, rope_n_elem, ak.shape[1], float(scale), _stream()))
+    return y
 
 
 def spec_accept(logits, window, out=None, token_inout=None, pos_inout=None):
