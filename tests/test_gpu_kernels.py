@@ -1,7 +1,9 @@
 """Per-kernel parity on the MI355X: the bf16 and quantized HIP ops through the C-ABI against the CPU oracle. The
 GPT-NeoX ops (lga_layernorm, lga_gelu), the fp32 path (csrc/fp32.hip, lga_argmax_f32, the fp32-row lga_embedding)
 are in tests/test_gpu_neox_kernels.py; the later kernel families have files of their own (test_gpu_int8.py,
-test_gpu_kv8.py, test_gpu_lora.py, ...).
+test_gpu_kv8.py, test_gpu_lora.py, ...). The attention kernels (lga_attention, the fused decode forms over bf16 and fp8
+caches, the MFMA prefill, the adapter prefix attention) on peaked and large-magnitude scores, where the softmax needs
+its running maximum and one key carries the whole weight, are in tests/test_gpu_attention_scores.py.
 
 Integer / byte work (quantizer packing, KV append, argmax) must be bit-exact; fp kernels are checked against an
 fp64/fp32 reference of the same op on the same bf16 inputs with the tolerance written in each test.
