@@ -31,6 +31,7 @@ typedef struct ihipStream_t* lga_stream_t; /* == hipStream_t */
 #define LGA_FMT_BF16 2 /* unquantized bf16 weight [N][K] (lga_q4_gemm_fused / lga_q4_gemm_swiglu only) */
 #define LGA_FMT_FP4 3 /* bitsandbytes FP4 code (get_4bit_type('fp4'), "bnb.fp4"), per-block fp32 absmax */
 #define LGA_FMT_INT8 4 /* LLM.int8: int8 [N][K], fp32 row absmax (the lga_int8_* entry points only) */
+#define LGA_FMT_FP8 5 /* fp8-g128: e4m3fn codes [N][K], bf16 power-of-two scale per 128 (the lga_fp8_* entry points only) */
 
 /* -- plumbing ---------------------------------------------------------------------------------------- */
 const char* lga_last_error_string(void);
@@ -143,6 +144,29 @@ int lga_int8_quantize_act(const void* x, void* xq, float* sx, int* col_flags, in
 int lga_int8_gemm(const void* x, const void* xq, const float* sx, const int* cols, const int* count,
                   const void* qweight, const float* scales, const void* bias, const void* residual, void* y, int M,
                   int N, int K, lga_stream_t stream);
+
+/* -- fp8-g128: weight-only OCP fp8 (e4m3fn) Linears, bf16 activations (csrc/gemv_fp8.hip, csrc/gemm_fp8.hip) ---------
+ * Storage: codes [N][K] uint8 e4m3fn, scales [N][K / 128] bf16, each a power of two. Rule (the fp8 KV cache's, on
+ * every run of 128 consecutive weights of a row, after rounding the weight to bf16): amax = max |x_i| = m 2^E with m in
+ * [0.5, 1); s = 2^e, e = E - 9 if m <= 0.875 else E - 8, clamped to [-126, 127]; amax = 0 gives s = 1;
+ * code = e4m3fn(x / s), round to nearest even, nothing saturates. W'[n][k] = float(code) * s is exact in bf16 (groups
+ * with non-finite values or amax < 2^-100 are outside the contract). Every entry point computes what the lga_bf16_*
+ * one computes on W': fp32 accumulation of exact bf16 x bf16 products, in an order of its own, with the same bf16
+ * rounding points in the RMSNorm prologue and the bias / residual / SwiGLU epilogues. K % 128 == 0 everywhere; x,
+ * codes and norm_weight 16-B aligned; nothing is launched before the checks pass. */
+/* weight quantizer: w [N][K] fp32 (w_is_bf16 = 0) or bf16 (1) -> codes, scales */
+int lga_fp8_quantize(const void* w, int w_is_bf16, uint8_t* codes, void* scales, int N, int K, lga_stream_t stream);
+/* decode GEMV y (N) = x (K) . W'^T [+bias] [+residual]; K <= 32768; optional fused RMSNorm of x for K <= 12288 */
+int lga_fp8_gemv(const void* x, const uint8_t* codes, const void* scales, const void* bias, const void* residual,
+                 const void* norm_weight, float norm_eps, void* y, int N, int K, lga_stream_t stream);
+/* y = bf16(silu(bf16(x W1'^T))) * bf16(x W2'^T), the same K limits */
+int lga_fp8_gemv_swiglu(const void* x, const uint8_t* codes1, const void* scales1, const uint8_t* codes2,
+                        const void* scales2, const void* norm_weight, float norm_eps, void* y, int N, int K,
+                        lga_stream_t stream);
+/* prefill GEMM Y (M, N) = X (M, K) . W'^T [+bias] [+residual] on the bf16 MFMA, the code tile expanded in registers;
+ * M >= 2 */
+int lga_fp8_gemm(const void* x, const uint8_t* codes, const void* scales, const void* bias, const void* residual,
+                 void* y, int M, int N, int K, lga_stream_t stream);
 
 /* -- LoRA adapters (the reference's lit_gpt/lora.py: the unmerged LoRALinear / LoRAQKVLinear forward :170-177,
  *    :398-433 and LoRALinear.merge :140-149, under bf16-true) --------------------------------------------------

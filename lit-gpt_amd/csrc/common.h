@@ -101,6 +101,7 @@ int preload_sample();
 int preload_gemv();
 int preload_moe();
 int preload_adapter();
+int preload_fp8();
 
 }  // namespace lga
 

@@ -27,6 +27,7 @@ FMT_NF4 = 1  # bitsandbytes NF4 codebook, per-block fp32 absmax
 FMT_BF16 = 2  # (prefill GEMM only) unquantized bf16 weight
 FMT_FP4 = 3  # bitsandbytes FP4 code, per-block fp32 absmax
 FMT_INT8 = 4  # LLM.int8: int8 (N, K) + fp32 row absmax (the int8_* ops only)
+FMT_FP8 = 5  # fp8-g128: e4m3fn codes (N, K) + bf16 power-of-two scale per 128 weights (the fp8_* ops only)
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -60,6 +61,10 @@ SIGNATURES = {
     "lga_int8_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P],
     "lga_int8_quantize_act": [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P],
     "lga_int8_gemm": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "lga_fp8_quantize": [_P, _I, _P, _P, _I, _I, _P],
+    "lga_fp8_gemv": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
+    "lga_fp8_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
+    "lga_fp8_gemm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_lora_gemv": [_P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_lora_gemv_rows": [_P, _P, _F, _P, _P, _P, _P, _I, ctypes.c_longlong, ctypes.c_longlong, _F, _P, _P, _P, _I,
                            _I, _I, _I, _I, _P],
@@ -475,6 +480,70 @@ def int8_gemm(x, xq, sx, cols, count, qweight, scales, *, bias=None, residual=No
                                         _dev(scales, "scales", torch.float32), _opt(bias, "bias", torch.bfloat16),
                                         _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
                                         M, N, K, _stream()))
+    return y
+
+
+# ------------------------------------------------------------------------------------------------ fp8-g128
+FP8_GROUP = 128  # weights per scale
+FP8_MAX_K = 32768  # lga_fp8_gemv(_swiglu)
+FP8_NORM_MAX_K = 12288  # ... with the RMSNorm fused
+
+
+def fp8_quantize(weight: torch.Tensor):
+    """(N, K) fp32/bf16 device weight -> (e4m3fn codes uint8 (N, K), power-of-two scales bf16 (N, K / 128)) by the fp8
+    KV cache's rule on every 128 consecutive weights of a row (include/litgpt_amd.h)."""
+    N, K = weight.shape
+    if K % FP8_GROUP:
+        raise ValueError(f"fp8-g128: in_features={K} is not a multiple of {FP8_GROUP}")
+    w = weight.contiguous()
+    if w.dtype not in (torch.float32, torch.bfloat16):
+        w = w.float()
+    codes = torch.empty(N, K, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, K // FP8_GROUP, dtype=torch.bfloat16, device=w.device)
+    _check(load_library().lga_fp8_quantize(_dev(w, "weight"), int(w.dtype == torch.bfloat16), codes.data_ptr(),
+                                           scales.data_ptr(), N, K, _stream()))
+    return codes, scales
+
+
+def fp8_gemv(x, codes, scales, *, bias=None, residual=None, norm_weight=None, eps=1e-5, out=None):
+    """y (N,) = x (K,) . W'^T [+bias] [+residual] for W' = float(codes) * scales; optional fused RMSNorm of x
+    (K <= FP8_NORM_MAX_K)."""
+    N, K = codes.shape
+    y = out if out is not None else torch.empty(N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_fp8_gemv(_dev(x, "x", torch.bfloat16), _dev(codes, "codes", torch.uint8),
+                                       _dev(scales, "scales", torch.bfloat16), _opt(bias, "bias", torch.bfloat16),
+                                       _opt(residual, "residual", torch.bfloat16),
+                                       _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                       _dev(y, "y", torch.bfloat16), N, K, _stream()))
+    return y
+
+
+def fp8_gemv_swiglu(x, codes1, scales1, codes2, scales2, *, norm_weight=None, eps=1e-5, out=None):
+    """y (N,) = bf16(silu(bf16(x W1'^T))) * bf16(x W2'^T) with fp8 weights, optional fused RMSNorm of x."""
+    N, K = codes1.shape
+    if tuple(codes2.shape) != (N, K):
+        raise ValueError(f"fp8_gemv_swiglu: weight shapes differ {tuple(codes1.shape)} vs {tuple(codes2.shape)}")
+    y = out if out is not None else torch.empty(N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_fp8_gemv_swiglu(_dev(x, "x", torch.bfloat16), _dev(codes1, "codes1", torch.uint8),
+                                              _dev(scales1, "scales1", torch.bfloat16),
+                                              _dev(codes2, "codes2", torch.uint8),
+                                              _dev(scales2, "scales2", torch.bfloat16),
+                                              _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                              _dev(y, "y", torch.bfloat16), N, K, _stream()))
+    return y
+
+
+def fp8_gemm(x, codes, scales, *, bias=None, residual=None, out=None):
+    """Y (M, N) = X (M, K) . W'^T [+bias] [+residual] on the bf16 MFMA, the codes expanded in registers; M >= 2."""
+    M = x.shape[0]
+    N, K = codes.shape
+    if x.shape[1] != K:
+        raise ValueError(f"fp8_gemm: shapes x {tuple(x.shape)} codes {tuple(codes.shape)}")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_fp8_gemm(_dev(x, "x", torch.bfloat16), _dev(codes, "codes", torch.uint8),
+                                       _dev(scales, "scales", torch.bfloat16), _opt(bias, "bias", torch.bfloat16),
+                                       _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
+                                       M, N, K, _stream()))
     return y
 
 

@@ -1,5 +1,6 @@
 """Quantized Linears — the drop-ins for bitsandbytes' ``Linear4bit`` (4-bit weight-only) and ``Linear8bitLt``
-(``bnb.int8``, LLM.int8) — and how a Linear of each weight format (4-bit, int8, bf16, fp32) runs on the kernels
+(``bnb.int8``, LLM.int8), the weight-only fp8 Linear (``fp8-g128``) — and how a Linear of each weight format (4-bit,
+int8, fp8, bf16, fp32) runs on the kernels
 (``_Kernels``, ``kernels``, ``swiglu``).
 
 Reference boundary ("Operator boundary being replaced"): any object used where ``nn.Linear`` is
@@ -24,6 +25,11 @@ Modes:
                                               columns holding any |x| >= 6.0 kept in bf16 (the outlier
                                               decomposition of Linear8bitLt(has_fp16_weights=False,
                                               threshold=6.0), bf16 where bitsandbytes computes in fp16)
+  "fp8-g128"                                  weight-only OCP fp8 (``Fp8Linear``): e4m3fn codes with a power-of-two
+                                              bf16 scale per 128 weights of a row (the fp8 KV cache's rule); the
+                                              dequantized weight is exact in bf16 and activations stay bf16, so a
+                                              Linear computes what the bf16 one computes on that weight, at half
+                                              its bytes. in_features must be a multiple of 128
 Group sizes must divide in_features; for a TP row-shard whose width is not a multiple of the requested group
 (e.g. Llama-2-7B mlp.proj at TP=8: 1376) the largest of {128, 64, 32} that divides it is used.
 """
@@ -66,6 +72,7 @@ _MODES = {
     "bnb.fp4": (ops.FMT_FP4, 64),
     "bnb.fp4-dq": (ops.FMT_FP4, 64),
     "bnb.int8": (ops.FMT_INT8, 0),  # Int8Linear: one fp32 scale per row, no group
+    "fp8-g128": (ops.FMT_FP8, 128),  # Fp8Linear: e4m3 codes, one power-of-two bf16 scale per 128 weights
 }
 
 
@@ -290,6 +297,63 @@ class Int8Linear(_Kernels, nn.Module):
                 f"threshold={self.threshold}")
 
 
+class Fp8Linear(_Kernels, nn.Module):
+    """Weight-only fp8 Linear (``fp8-g128``): ``qweight`` (N, K) uint8 e4m3fn codes + ``scales`` (N, K / 128) bf16
+    powers of two on the GPU. Activations stay bf16; the Linear computes what ``Bf16Linear`` computes on the
+    dequantized weight ``float(code) * scale`` (exact in bf16).
+
+    One token -> ``lga_fp8_gemv`` (RMSNorm / bias / residual fused), several -> the bf16 MFMA GEMM ``lga_fp8_gemm``
+    that expands the code tile in registers; fc_1 || fc_2 of one token -> ``lga_fp8_gemv_swiglu``, of several two
+    GEMMs and ``lga_swiglu``."""
+
+    def __init__(self, in_features: int, out_features: int, bias: Optional[torch.Tensor] = None, device=None):
+        super().__init__()
+        if in_features % ops.FP8_GROUP:
+            raise ValueError(f"in_features={in_features} is not a multiple of {ops.FP8_GROUP}; fp8-g128 scales runs "
+                             f"of {ops.FP8_GROUP} weights")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("qweight", torch.empty(out_features, in_features, dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.empty(out_features, in_features // ops.FP8_GROUP, dtype=torch.bfloat16,
+                                                   device=device))
+        self.bias = None if bias is None else nn.Parameter(bias.to(torch.bfloat16), requires_grad=False)
+
+    @property
+    def weight(self) -> torch.Tensor:
+        return self.qweight
+
+    @classmethod
+    def from_float(cls, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                   device: Optional[torch.device] = None, *, mode: str = "fp8-g128") -> "Fp8Linear":
+        N, K = weight.shape
+        if K % ops.FP8_GROUP:  # before anything touches the device
+            raise ValueError(f"in_features={K} is not a multiple of {ops.FP8_GROUP}; fp8-g128 scales runs of "
+                             f"{ops.FP8_GROUP} weights")
+        device = device or (weight.device if weight.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        m = cls(K, N, None if bias is None else bias.detach().to(device), device=device)
+        qw, sc = ops.fp8_quantize(weight.detach().to(device))
+        m.qweight.copy_(qw)
+        m.scales.copy_(sc)
+        return m
+
+    def gemv_fuses_norm(self, dual: bool = False) -> bool:
+        """lga_fp8_gemv(_swiglu) takes the RMSNorm of rows up to K = 12288."""
+        return self.in_features <= ops.FP8_NORM_MAX_K
+
+    def gemv(self, x, res, norm_weight, eps):
+        return ops.fp8_gemv(x, self.qweight, self.scales, bias=self.bias, residual=res, norm_weight=norm_weight,
+                            eps=eps)
+
+    def gemm(self, x, res):
+        return ops.fp8_gemm(x, self.qweight, self.scales, bias=self.bias, residual=res)
+
+    def gemv_swiglu(self, o, x, norm_weight, eps):
+        return ops.fp8_gemv_swiglu(x, self.qweight, self.scales, o.qweight, o.scales, norm_weight=norm_weight,
+                                   eps=eps)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}, fp8 e4m3, group={ops.FP8_GROUP}"
+
+
 class _DenseLinear(_Kernels):
     """The per-call adapter of a device ``nn.Linear`` (bf16 or fp32 weights) to the ``_Kernels`` skeleton."""
 
@@ -418,11 +482,11 @@ class QuantizedPrecision:
         self.mode, self.dtype = mode, dtype
 
     def convert_module(self, module: nn.Module, device: Optional[torch.device] = None) -> nn.Module:
-        """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` (``Int8Linear`` for ``bnb.int8``)
-        quantized on ``device``."""
+        """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` (``Int8Linear`` for ``bnb.int8``,
+        ``Fp8Linear`` for ``fp8-g128``) quantized on ``device``."""
         for name, child in list(module.named_children()):
             if isinstance(child, nn.Linear):
-                cls = Int8Linear if self.mode == "bnb.int8" else QuantLinear
+                cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear}.get(self.mode, QuantLinear)
                 setattr(module, name, cls.from_float(child.weight, child.bias, mode=self.mode, device=device))
             else:
                 self.convert_module(child, device)
