@@ -163,6 +163,14 @@ int lga_fp8_gemv(const void* x, const uint8_t* codes, const void* scales, const 
 int lga_fp8_gemv_swiglu(const void* x, const uint8_t* codes1, const void* scales1, const uint8_t* codes2,
                         const void* scales2, const void* norm_weight, float norm_eps, void* y, int N, int K,
                         lga_stream_t stream);
+/* the two GEMVs over M = 1..8 activation rows in one pass over the weights (batched decode, the speculative verify
+ * window): x (M, K), residual (M, N), y (M, N), the same K limits. Row r has the bits of the one-row call on x[r] with
+ * residual[r], for every M */
+int lga_fp8_gemv_rows(const void* x, const uint8_t* codes, const void* scales, const void* bias, const void* residual,
+                      const void* norm_weight, float norm_eps, void* y, int M, int N, int K, lga_stream_t stream);
+int lga_fp8_gemv_swiglu_rows(const void* x, const uint8_t* codes1, const void* scales1, const uint8_t* codes2,
+                             const void* scales2, const void* norm_weight, float norm_eps, void* y, int M, int N,
+                             int K, lga_stream_t stream);
 /* prefill GEMM Y (M, N) = X (M, K) . W'^T [+bias] [+residual] on the bf16 MFMA, the code tile expanded in registers;
  * M >= 2 */
 int lga_fp8_gemm(const void* x, const uint8_t* codes, const void* scales, const void* bias, const void* residual,

@@ -783,15 +783,16 @@ def _cli(argv=None) -> None:
     p.add_argument("--synthetic", default=None, help="random-init model of this registered config name")
     p.add_argument("--prompt_len", type=int, default=16)
     p.add_argument("--batch_size", type=int, default=1,
-                   help="decode the samples this many at a time (1..4) through generate_batch")
+                   help="decode the samples this many at a time (1..4) through generate_batch (a 4-bit or fp8-g128 "
+                        "--quantize: quantize.ROWS_MODES)")
     p.add_argument("--prompts_file", type=Path, default=None,
                    help="one prompt per line (with --synthetic: one prompt length per line); all of them run through "
-                        "--batch_size slots with continuous batching (generate_continuous)")
+                        "--batch_size slots with continuous batching (generate_continuous; 4-bit or fp8-g128 weights)")
     p.add_argument("--kv_cache", default="bf16", choices=sorted(KV_CACHE_DTYPES),
                    help="KV cache format: fp8 = e4m3 codes + one power-of-two scale per row (0.516 x the bytes)")
     p.add_argument("--share_prompt", action="store_true",
                    help="with --batch_size > 1: prefill the prompt once for all --num_samples samples "
-                        "(generate_samples) instead of once per sample")
+                        "(generate_samples) instead of once per sample (4-bit or fp8-g128 weights)")
     a = p.parse_args(argv)
     main(a.prompt, num_samples=a.num_samples, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
          temperature=a.temperature, checkpoint_dir=a.checkpoint_dir, quantize=a.quantize, precision=a.precision,

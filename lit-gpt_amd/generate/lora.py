@@ -116,11 +116,11 @@ def serve(lora_paths: Sequence[Path], prompts_file: Path, batch_size: int = MAX_
                                   "into it; they run next to the quantized weight")
     if quantize is None:
         raise NotImplementedError("--lora_paths with a bf16 base: the batched decode streams 4-bit weights only "
-                                  f"(--quantize {quantize_mod.ROWS_MODES})")
+                                  f"(--quantize {quantize_mod.ROWS_MODES_4BIT})")
     fmt, _ = quantize_mod.parse_mode(quantize)
     if fmt not in (ops.FMT_Q4G, ops.FMT_NF4, ops.FMT_FP4):
         raise NotImplementedError(f"--lora_paths with --quantize {quantize}: the batched decode streams 4-bit weights "
-                                  f"only ({quantize_mod.ROWS_MODES})")
+                                  f"only ({quantize_mod.ROWS_MODES_4BIT})")
     if not 1 <= batch_size <= MAX_BATCH:
         raise NotImplementedError(f"--batch_size {batch_size}: the batched decode runs 1..{MAX_BATCH} sequences per step")
     lora_paths = [Path(p) for p in lora_paths]

@@ -305,7 +305,7 @@ def main(prompt: str = "What food do llamas eat?", *, max_new_tokens: int = 50,
     from lit_gpt import ops
 
     if (precision or "bf16-true") != "bf16-true":
-        raise NotImplementedError("speculative decoding runs 4-bit weights under bf16-true")
+        raise NotImplementedError("speculative decoding runs 4-bit or fp8-g128 weights under bf16-true")
     if not 0.0 < top_p <= 1.0:
         raise ValueError(f"--top_p must be in (0, 1], got {top_p}")
     if temperature > 0.0 and ((top_k is None and top_p == 1.0) or
@@ -383,8 +383,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--prompt", default="What food do llamas eat?")
     p.add_argument("--max_new_tokens", type=int, default=50)
     p.add_argument("--checkpoint_dir", type=Path, default=Path("checkpoints/stabilityai/stablelm-base-alpha-3b"))
-    p.add_argument("--quantize", default="int4-g128", help="the target's 4-bit format (the verify window streams "
-                                                           "plain 4-bit Linears)")
+    p.add_argument("--quantize", default="int4-g128", help="the target's weight format: 4-bit or fp8-g128 (the verify "
+                                                           "window streams plain Linears of "
+                                                           "quantize.ROWS_MODES)")
     p.add_argument("--precision", default=None)
     p.add_argument("--temperature", type=float, default=0.0,
                    help="0: greedy; > 0 samples as generate/base.py does and needs --top_k")
@@ -397,7 +398,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--draft", default=None, choices=["ngram"], help="prompt-lookup drafting on the host")
     p.add_argument("--draft_checkpoint_dir", type=Path, default=None, help="a draft model checkpoint")
     p.add_argument("--draft_synthetic", default=None, help="random-init draft model of this registered config name")
-    p.add_argument("--draft_quantize", default="int4-g128")
+    p.add_argument("--draft_quantize", default="int4-g128", help="the draft model's weight format (any --quantize of "
+                                                                 "this build: it decodes one row at a time)")
     p.add_argument("--speculate", type=int, default=DEFAULT_SPECULATE,
                    help=f"drafts per round (1..{GPT.MAX_WINDOW - 1})")
     p.add_argument("--kv_cache", default="bf16", choices=["bf16", "fp8"],

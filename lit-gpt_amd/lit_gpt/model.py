@@ -146,7 +146,7 @@ class GPT(nn.Module):
 
     def _batch_check(self, B: int) -> None:
         """What the batched route (B > 1) covers: up to MAX_BATCH sequences, dense RMSNorm / LLaMAMLP blocks whose
-        Linears are all 4-bit ``QuantLinear`` and carry no hooks. Everything else is refused here, before any launch."""
+        Linears are all 4-bit ``QuantLinear`` or ``Fp8Linear`` and carry no hooks. Everything else is refused here, before any launch."""
         if B > self.MAX_BATCH:
             raise NotImplementedError(f"batch size {B}: the MI355X batched decode runs at most {self.MAX_BATCH} "
                                       "sequences per step")
@@ -158,14 +158,16 @@ class GPT(nn.Module):
         the batch) counts as its base Linear; a single-adapter ``LoraLinear`` stays refused."""
         from lit_gpt.lora import MultiLoraLinear  # (lit_gpt.lora imports this package)
 
-        def four_bit(lin, name):
+        def four_bit(lin, name):  # ... or fp8-g128: the formats with a rows GEMV
+            plain = (quantize.QuantLinear, quantize.Fp8Linear)
             if adapters and isinstance(lin, MultiLoraLinear) and not lin._forward_hooks:
-                lin = lin.base
-            if type(lin) is not quantize.QuantLinear or lin._forward_hooks:
+                lin, plain = lin.base, (quantize.QuantLinear,)  # several adapters: over a 4-bit base only
+            if type(lin) not in plain or lin._forward_hooks:
                 raise NotImplementedError(
                     f"{what} with {name} a {type(lin).__name__}: the multi-row decode GEMV streams plain "
-                    f"4-bit Linears only (--quantize {quantize.ROWS_MODES}); LoRA-attached, bnb.int8, bf16 and fp32 "
-                    "Linears decode one sequence at a time (a batch takes adapters attached with lora.attach_many)")
+                    f"4-bit Linears only, or fp8-g128 ones (--quantize {quantize.ROWS_MODES}); LoRA-attached, "
+                    "bnb.int8, bf16 and fp32 Linears decode one sequence at a time (a batch takes adapters attached "
+                    "with lora.attach_many)")
 
         for i, blk in enumerate(self.transformer.h):
             if blk.config.parallel_residual or not isinstance(blk.norm_1, RMSNorm):

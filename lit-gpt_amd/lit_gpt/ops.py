@@ -64,6 +64,8 @@ SIGNATURES = {
     "lga_fp8_quantize": [_P, _I, _P, _P, _I, _I, _P],
     "lga_fp8_gemv": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
     "lga_fp8_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
+    "lga_fp8_gemv_rows": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _P],
+    "lga_fp8_gemv_swiglu_rows": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _P],
     "lga_fp8_gemm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_lora_gemv": [_P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_lora_gemv_rows": [_P, _P, _F, _P, _P, _P, _P, _I, ctypes.c_longlong, ctypes.c_longlong, _F, _P, _P, _P, _I,
@@ -530,6 +532,39 @@ def fp8_gemv_swiglu(x, codes1, scales1, codes2, scales2, *, norm_weight=None, ep
                                               _dev(scales2, "scales2", torch.bfloat16),
                                               _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
                                               _dev(y, "y", torch.bfloat16), N, K, _stream()))
+    return y
+
+
+def fp8_gemv_rows(x, codes, scales, *, bias=None, residual=None, norm_weight=None, eps=1e-5, out=None):
+    """Y (M, N) = X (M, K) . W'^T [+bias] [+residual (M, N)] for 1 <= M <= 8 rows in one pass over the weights; row r
+    has the bits of ``fp8_gemv(x[r], ..., residual=residual[r])``."""
+    N, K = codes.shape
+    M = _gemv_rows(x, K, "fp8_gemv_rows")
+    if residual is not None and tuple(residual.shape) != (M, N):
+        raise ValueError(f"fp8_gemv_rows: residual must be ({M}, {N}), got {tuple(residual.shape)}")
+    y = _rows_out(out, M, N, x, "fp8_gemv_rows")
+    _check(load_library().lga_fp8_gemv_rows(_dev(x, "x", torch.bfloat16), _dev(codes, "codes", torch.uint8),
+                                            _dev(scales, "scales", torch.bfloat16), _opt(bias, "bias", torch.bfloat16),
+                                            _opt(residual, "residual", torch.bfloat16),
+                                            _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                            _dev(y, "y", torch.bfloat16), M, N, K, _stream()))
+    return y
+
+
+def fp8_gemv_swiglu_rows(x, codes1, scales1, codes2, scales2, *, norm_weight=None, eps=1e-5, out=None):
+    """Y (M, N) = bf16(silu(bf16(X W1'^T))) * bf16(X W2'^T) for 1 <= M <= 8 rows in one pass over both weights; row r
+    has the bits of ``fp8_gemv_swiglu(x[r], ...)``."""
+    N, K = codes1.shape
+    M = _gemv_rows(x, K, "fp8_gemv_swiglu_rows")
+    if tuple(codes2.shape) != (N, K):
+        raise ValueError(f"fp8_gemv_swiglu_rows: weight shapes differ {tuple(codes1.shape)} vs {tuple(codes2.shape)}")
+    y = _rows_out(out, M, N, x, "fp8_gemv_swiglu_rows")
+    _check(load_library().lga_fp8_gemv_swiglu_rows(_dev(x, "x", torch.bfloat16), _dev(codes1, "codes1", torch.uint8),
+                                                   _dev(scales1, "scales1", torch.bfloat16),
+                                                   _dev(codes2, "codes2", torch.uint8),
+                                                   _dev(scales2, "scales2", torch.bfloat16),
+                                                   _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                                   _dev(y, "y", torch.bfloat16), M, N, K, _stream()))
     return y
 
 

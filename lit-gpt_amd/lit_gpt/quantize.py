@@ -77,7 +77,8 @@ _MODES = {
 
 
 # the --quantize modes whose Linears the batched decode route (B > 1) runs
-ROWS_MODES = "int4-g128/64/32, nf4, bnb.nf4, bnb.nf4-dq, bnb.fp4, bnb.fp4-dq"
+ROWS_MODES_4BIT = "int4-g128/64/32, nf4, bnb.nf4, bnb.nf4-dq, bnb.fp4, bnb.fp4-dq"  # ... with lora.attach_many
+ROWS_MODES = ROWS_MODES_4BIT + ", fp8-g128"
 
 
 def parse_mode(mode: str):
@@ -140,12 +141,13 @@ class _Kernels:
         return self.gemv_rows(x2, res, norm_weight, norm_eps).view(*lead, self.out_features)
 
     def gemv_rows(self, x, res, norm_weight, eps):
-        """Up to 8 rows in one pass over the weights (batched decode): the 4-bit formats have the kernel."""
+        """Up to 8 rows in one pass over the weights (batched decode): the 4-bit formats and fp8-g128 have the
+        kernel."""
         raise NotImplementedError(f"batched decode (batch size > 1) with a {self.kind}: the multi-row decode GEMV "
-                                  f"streams 4-bit weights only ({ROWS_MODES})")
+                                  f"streams 4-bit and fp8-g128 weights only ({ROWS_MODES})")
 
     def gemv_swiglu_rows(self, o, x, norm_weight, eps):
-        return self.gemv_rows(x, None, norm_weight, eps)  # (raises: only QuantLinear overrides the pair)
+        return self.gemv_rows(x, None, norm_weight, eps)  # (raises: QuantLinear and Fp8Linear override the pair)
 
     def pairs_with(self, o: "_Kernels") -> bool:
         """Whether ``self`` and ``o`` (fc_1, fc_2) can share one dual launch: here what every format asks."""
@@ -342,6 +344,14 @@ class Fp8Linear(_Kernels, nn.Module):
     def gemv(self, x, res, norm_weight, eps):
         return ops.fp8_gemv(x, self.qweight, self.scales, bias=self.bias, residual=res, norm_weight=norm_weight,
                             eps=eps)
+
+    def gemv_rows(self, x, res, norm_weight, eps):
+        return ops.fp8_gemv_rows(x, self.qweight, self.scales, bias=self.bias, residual=res, norm_weight=norm_weight,
+                                 eps=eps)
+
+    def gemv_swiglu_rows(self, o, x, norm_weight, eps):
+        return ops.fp8_gemv_swiglu_rows(x, self.qweight, self.scales, o.qweight, o.scales, norm_weight=norm_weight,
+                                        eps=eps)
 
     def gemm(self, x, res):
         return ops.fp8_gemm(x, self.qweight, self.scales, bias=self.bias, residual=res)

@@ -8,7 +8,8 @@ usage: python tools/batch_decode.py kernels [--out FILE.json]
            graph, so no copy is served from the MALL), in one process. Prints the two criteria per shape and M:
            rows(M) < M x one-row and rows(M) < GEMM(M).
        python tools/batch_decode.py e2e [--batches 1,2,4] [--prompt_len 2048] [--steps 255] [--out FILE.json]
-           synthetic Llama-2-7B int4-g128, greedy: aggregate decode tokens/s of generate (B = 1) and generate_batch
+           synthetic Llama-2-7B int4-g128 (--quantize: another rows format, e.g. fp8-g128), greedy: aggregate decode
+           tokens/s of generate (B = 1) and generate_batch
            (B > 1), the prefill excluded (timed apart), median of 3 runs after one warm-up run per B.
            --attn both: every B > 1 twice in the same process, alternated run by run — the one-launch batch attention
            (lit_gpt.model.batch_attention) and the per-sequence loop (LGA_BATCH_ATTN=0, the previous behaviour).
@@ -397,14 +398,14 @@ def continuous(out, prompt_len=512, slots=4):
     _write(out, result)
 
 
-def e2e(out, batches, prompt_len, steps, attn_mode="default"):
+def e2e(out, batches, prompt_len, steps, attn_mode="default", quantize="int4-g128"):
     import lit_gpt.model as lm
     from generate.base import build_model, generate, generate_batch
     from lit_gpt import Config
 
     dev = torch.device("cuda")
     cfg = Config.from_name("Llama-2-7b-hf")
-    model = build_model(cfg, quantize="int4-g128", device=dev, max_seq_length=prompt_len + steps + 1)
+    model = build_model(cfg, quantize=quantize, device=dev, max_seq_length=prompt_len + steps + 1)
     g = torch.Generator(device="cpu").manual_seed(1234)
     prompts = [torch.randint(0, cfg.vocab_size, (prompt_len,), generator=g, dtype=torch.int32).to(dev)
                for _ in range(max(batches))]
@@ -421,7 +422,7 @@ def e2e(out, batches, prompt_len, steps, attn_mode="default"):
         assert all(y.numel() == prompt_len + n_new for y in ys)
         return time.perf_counter() - t0
 
-    result = {"what": "synthetic Llama-2-7B int4-g128, greedy; decode time = run(steps + 1 tokens) - run(1 token), "
+    result = {"what": f"synthetic Llama-2-7B {quantize}, greedy; decode time = run(steps + 1 tokens) - run(1 token), "
                       "median of 3 after a warm-up run", "prompt_len": prompt_len, "steps": steps, "batches": {}}
     result["batch_attention_default"] = bool(lm.batch_attention)
     for B in batches:
@@ -475,6 +476,7 @@ if __name__ == "__main__":
     p.add_argument("--batches", default="1,2,4")
     p.add_argument("--prompt_len", type=int, default=2048)
     p.add_argument("--steps", type=int, default=255)
+    p.add_argument("--quantize", default="int4-g128", help="e2e: the weight format (a mode of quantize.ROWS_MODES)")
     p.add_argument("--attn", default="default", choices=("default", "both"),
                    help="e2e: 'both' alternates the batch attention launch and the per-sequence loop")
     a = p.parse_args()
@@ -489,4 +491,4 @@ if __name__ == "__main__":
     elif a.mode == "continuous":
         continuous(a.out)
     else:
-        e2e(a.out, [int(b) for b in a.batches.split(",")], a.prompt_len, a.steps, a.attn)
+        e2e(a.out, [int(b) for b in a.batches.split(",")], a.prompt_len, a.steps, a.attn, a.quantize)
