@@ -32,6 +32,7 @@ typedef struct ihipStream_t* lga_stream_t; /* == hipStream_t */
 #define LGA_FMT_FP4 3 /* bitsandbytes FP4 code (get_4bit_type('fp4'), "bnb.fp4"), per-block fp32 absmax */
 #define LGA_FMT_INT8 4 /* LLM.int8: int8 [N][K], fp32 row absmax (the lga_int8_* entry points only) */
 #define LGA_FMT_FP8 5 /* fp8-g128: e4m3fn codes [N][K], bf16 power-of-two scale per 128 (the lga_fp8_* entry points only) */
+#define LGA_FMT_MXFP4 6 /* mxfp4: e2m1 code pairs [N][K / 2], e8m0 scale byte per 32 (the lga_mxfp4_* entry points only) */
 
 /* -- plumbing ---------------------------------------------------------------------------------------- */
 const char* lga_last_error_string(void);
@@ -175,6 +176,33 @@ int lga_fp8_gemv_swiglu_rows(const void* x, const uint8_t* codes1, const void* s
  * M >= 2 */
 int lga_fp8_gemm(const void* x, const uint8_t* codes, const void* scales, const void* bias, const void* residual,
                  void* y, int M, int N, int K, lga_stream_t stream);
+
+/* -- mxfp4: weight-only OCP MXFP4 Linears, bf16 activations (csrc/gemv_mxfp4.hip, csrc/gemm_mxfp4.hip) ---------------
+ * Storage: codes [N][K / 2] uint8, two e2m1 codes per byte, the even column in the low nibble (bit 3 sign, bits 2:1
+ * exponent, bit 0 mantissa: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6); scales [N][K / 32] uint8 e8m0, byte e = 2^(e - 127),
+ * one per block of 32 consecutive weights of a row. Rule (OCP MX v1.0 6.3, on fp32 values; bf16 input converts
+ * exactly): amax = max |w_i| of the block; amax = 0 gives e = 127 and all codes 0; else s = floor(log2 amax) - 2
+ * clamped to [-125, 125], e = s + 127; code_i = w_i 2^-s rounded to the nearest e2m1 value, ties to the even code,
+ * magnitudes above 6 saturating to 6; the code's sign bit is the sign bit of w_i, also where the magnitude rounds to
+ * zero. W'[n][k] = e2m1(code) * 2^(e - 127) is zero or a normal bf16 (blocks with non-finite values are outside the
+ * contract; the kernels take any e in [1, 254] the conversion keeps normal). Every entry point computes what the
+ * lga_bf16_* one computes on W': fp32 accumulation of exact bf16 x bf16 products, in an order of its own, with the
+ * same bf16 rounding points in the RMSNorm prologue and the bias / residual / SwiGLU epilogues. K % 32 == 0
+ * everywhere; x, codes and norm_weight 16-B aligned (scales: none); nothing is launched before the checks pass. */
+/* weight quantizer: w [N][K] fp32 (w_is_bf16 = 0) or bf16 (1) -> codes, scales */
+int lga_mxfp4_quantize(const void* w, int w_is_bf16, uint8_t* codes, uint8_t* scales, int N, int K,
+                       lga_stream_t stream);
+/* decode GEMV y (N) = x (K) . W'^T [+bias] [+residual]; K <= 32768; optional fused RMSNorm of x for K <= 12288 */
+int lga_mxfp4_gemv(const void* x, const uint8_t* codes, const uint8_t* scales, const void* bias, const void* residual,
+                   const void* norm_weight, float norm_eps, void* y, int N, int K, lga_stream_t stream);
+/* y = bf16(silu(bf16(x W1'^T))) * bf16(x W2'^T), the same K limits */
+int lga_mxfp4_gemv_swiglu(const void* x, const uint8_t* codes1, const uint8_t* scales1, const uint8_t* codes2,
+                          const uint8_t* scales2, const void* norm_weight, float norm_eps, void* y, int N, int K,
+                          lga_stream_t stream);
+/* prefill GEMM Y (M, N) = X (M, K) . W'^T [+bias] [+residual] on the bf16 MFMA, the code tile expanded in registers;
+ * M >= 2 */
+int lga_mxfp4_gemm(const void* x, const uint8_t* codes, const uint8_t* scales, const void* bias, const void* residual,
+                   void* y, int M, int N, int K, lga_stream_t stream);
 
 /* -- LoRA adapters (the reference's lit_gpt/lora.py: the unmerged LoRALinear / LoRAQKVLinear forward :170-177,
  *    :398-433 and LoRALinear.merge :140-149, under bf16-true) --------------------------------------------------

@@ -102,6 +102,7 @@ int preload_gemv();
 int preload_moe();
 int preload_adapter();
 int preload_fp8();
+int preload_mxfp4();
 
 }  // namespace lga
 

@@ -1,6 +1,6 @@
 """Quantized Linears — the drop-ins for bitsandbytes' ``Linear4bit`` (4-bit weight-only) and ``Linear8bitLt``
-(``bnb.int8``, LLM.int8), the weight-only fp8 Linear (``fp8-g128``) — and how a Linear of each weight format (4-bit,
-int8, fp8, bf16, fp32) runs on the kernels
+(``bnb.int8``, LLM.int8), the weight-only fp8 and MXFP4 Linears (``fp8-g128``, ``mxfp4``) — and how a Linear of each
+weight format (4-bit, int8, fp8, mxfp4, bf16, fp32) runs on the kernels
 (``_Kernels``, ``kernels``, ``swiglu``).
 
 Reference boundary ("Operator boundary being replaced"): any object used where ``nn.Linear`` is
@@ -30,6 +30,10 @@ Modes:
                                               dequantized weight is exact in bf16 and activations stay bf16, so a
                                               Linear computes what the bf16 one computes on that weight, at half
                                               its bytes. in_features must be a multiple of 128
+  "mxfp4"                                     weight-only OCP MXFP4 (``Mxfp4Linear``): e2m1 codes, two per byte, with
+                                              one e8m0 power-of-two scale per 32 weights of a row (MX v1.0 §6.3);
+                                              4.25 bits per weight, the dequantized weight exact in bf16, bf16
+                                              activations. in_features must be a multiple of 32
 Group sizes must divide in_features; for a TP row-shard whose width is not a multiple of the requested group
 (e.g. Llama-2-7B mlp.proj at TP=8: 1376) the largest of {128, 64, 32} that divides it is used.
 """
@@ -73,6 +77,7 @@ _MODES = {
     "bnb.fp4-dq": (ops.FMT_FP4, 64),
     "bnb.int8": (ops.FMT_INT8, 0),  # Int8Linear: one fp32 scale per row, no group
     "fp8-g128": (ops.FMT_FP8, 128),  # Fp8Linear: e4m3 codes, one power-of-two bf16 scale per 128 weights
+    "mxfp4": (ops.FMT_MXFP4, 32),  # Mxfp4Linear: e2m1 codes, one e8m0 scale byte per 32 weights
 }
 
 
@@ -364,6 +369,65 @@ class Fp8Linear(_Kernels, nn.Module):
         return f"in_features={self.in_features}, out_features={self.out_features}, fp8 e4m3, group={ops.FP8_GROUP}"
 
 
+class Mxfp4Linear(_Kernels, nn.Module):
+    """Weight-only MXFP4 Linear (``mxfp4``): ``qweight`` (N, K / 2) uint8, two e2m1 codes per byte with the even
+    column in the low nibble, + ``scales`` (N, K / 32) uint8 e8m0 on the GPU. Activations stay bf16; the Linear
+    computes what ``Bf16Linear`` computes on the dequantized weight ``e2m1(code) * 2^(scale - 127)`` (exact in bf16).
+
+    One token -> ``lga_mxfp4_gemv`` (RMSNorm / bias / residual fused), several -> the bf16 MFMA GEMM
+    ``lga_mxfp4_gemm`` that expands the code tile in registers; fc_1 || fc_2 of one token ->
+    ``lga_mxfp4_gemv_swiglu``, of several two GEMMs and ``lga_swiglu``. There is no multi-row decode GEMV: batched and
+    speculative decoding refuse the format (``_Kernels.gemv_rows``)."""
+
+    def __init__(self, in_features: int, out_features: int, bias: Optional[torch.Tensor] = None, device=None):
+        super().__init__()
+        if in_features % ops.MXFP4_GROUP:
+            raise ValueError(f"in_features={in_features} is not a multiple of {ops.MXFP4_GROUP}; mxfp4 scales blocks "
+                             f"of {ops.MXFP4_GROUP} weights")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("qweight", torch.empty(out_features, in_features // 2, dtype=torch.uint8, device=device))
+        self.register_buffer("scales", torch.empty(out_features, in_features // ops.MXFP4_GROUP, dtype=torch.uint8,
+                                                   device=device))
+        self.bias = None if bias is None else nn.Parameter(bias.to(torch.bfloat16), requires_grad=False)
+
+    @property
+    def weight(self) -> torch.Tensor:
+        return self.qweight
+
+    @classmethod
+    def from_float(cls, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                   device: Optional[torch.device] = None, *, mode: str = "mxfp4") -> "Mxfp4Linear":
+        N, K = weight.shape
+        if K % ops.MXFP4_GROUP:  # before anything touches the device
+            raise ValueError(f"in_features={K} is not a multiple of {ops.MXFP4_GROUP}; mxfp4 scales blocks of "
+                             f"{ops.MXFP4_GROUP} weights")
+        device = device or (weight.device if weight.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        m = cls(K, N, None if bias is None else bias.detach().to(device), device=device)
+        qw, sc = ops.mxfp4_quantize(weight.detach().to(device))
+        m.qweight.copy_(qw)
+        m.scales.copy_(sc)
+        return m
+
+    def gemv_fuses_norm(self, dual: bool = False) -> bool:
+        """lga_mxfp4_gemv(_swiglu) takes the RMSNorm of rows up to K = 12288."""
+        return self.in_features <= ops.MXFP4_NORM_MAX_K
+
+    def gemv(self, x, res, norm_weight, eps):
+        return ops.mxfp4_gemv(x, self.qweight, self.scales, bias=self.bias, residual=res, norm_weight=norm_weight,
+                              eps=eps)
+
+    def gemm(self, x, res):
+        return ops.mxfp4_gemm(x, self.qweight, self.scales, bias=self.bias, residual=res)
+
+    def gemv_swiglu(self, o, x, norm_weight, eps):
+        return ops.mxfp4_gemv_swiglu(x, self.qweight, self.scales, o.qweight, o.scales, norm_weight=norm_weight,
+                                     eps=eps)
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, mxfp4 e2m1, "
+                f"e8m0 block={ops.MXFP4_GROUP}")
+
+
 class _DenseLinear(_Kernels):
     """The per-call adapter of a device ``nn.Linear`` (bf16 or fp32 weights) to the ``_Kernels`` skeleton."""
 
@@ -440,7 +504,8 @@ def kernels(lin: nn.Module) -> _Kernels:
         return (F32Linear if lin.weight.dtype == torch.float32 else Bf16Linear)(lin)
     raise NotImplementedError(
         "Linear without MI355X weights: move the model to the GPU in bf16, or convert it with "
-        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8').convert_module(model) (the --quantize "
+        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8' | 'fp8-g128' | 'mxfp4')"
+        ".convert_module(model) (the --quantize "
         "flag)")
 
 
@@ -493,10 +558,10 @@ class QuantizedPrecision:
 
     def convert_module(self, module: nn.Module, device: Optional[torch.device] = None) -> nn.Module:
         """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` (``Int8Linear`` for ``bnb.int8``,
-        ``Fp8Linear`` for ``fp8-g128``) quantized on ``device``."""
+        ``Fp8Linear`` for ``fp8-g128``, ``Mxfp4Linear`` for ``mxfp4``) quantized on ``device``."""
         for name, child in list(module.named_children()):
             if isinstance(child, nn.Linear):
-                cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear}.get(self.mode, QuantLinear)
+                cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear, "mxfp4": Mxfp4Linear}.get(self.mode, QuantLinear)
                 setattr(module, name, cls.from_float(child.weight, child.bias, mode=self.mode, device=device))
             else:
                 self.convert_module(child, device)
