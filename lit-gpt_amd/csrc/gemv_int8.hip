@@ -1,8 +1,8 @@
 // Batch-1 decode GEMV over LLM.int8 weights (--quantize bnb.int8): int8 [N][K] + fp32 row absmax, the activation
 // row quantized per call with the outlier columns (|x| >= threshold) kept in bf16 (include/litgpt_amd.h has the
-// arithmetic). Structure follows gemv_bf16.hip — a pure weight stream in 16-B chunks (16 weights each), the weight
-// loads of pass 0 issued before anything waits on x:
-//  * prologue (while the weights stream): optional RMSNorm, then ONE more block reduction gives s_x = max |x| over
+// arithmetic). A pure weight stream in 16-B chunks (16 weights each) built from the pieces of the pass skeleton
+// (gemv_pass.h: the x / norm fetch, the RMS recipe, the weight issue, the pass loop, the launcher); its own are
+//  * prologue (while the weights stream): after the optional RMSNorm, ONE more block reduction gives s_x = max |x| over
 //    the non-outlier columns and whether any outlier exists; LDS then holds the int8 image of x (0 in outlier
 //    columns), the bf16 row, and one outlier bit per column;
 //  * dot: v_dot4 on packed int8 (4 per chunk and row), exact int32 accumulation, an integer transposed butterfly;
@@ -11,23 +11,14 @@
 //    skipped block-wide when the row has no outlier;
 //  * epilogue: float(acc) * ((s_x * s_w) / 16129) + outliers + bias, residual, SwiGLU with the bf16 rounding points
 //    of the other Linears.
-#include "decode_ops.h"
+#include "gemv_pass.h"
 #include "int8_ops.h"
 
 namespace lga {
 
 struct GemvI8Args {
-  const uint16_t* x;         // [K] bf16
-  const int8_t* w;           // [N][K] int8
-  const int8_t* w2;          // dual: fc_2
-  const float* sw;           // [N] row absmax
-  const float* sw2;          // dual: fc_2
-  const uint16_t* bias;      // [N] or null
-  const uint16_t* residual;  // [N] or null
-  const uint16_t* norm_w;    // [K] or null (fused RMSNorm)
-  uint16_t* y;               // [N]
-  int N, K;
-  float eps, thr;
+  GemvPassArgs g;  // w: [N][K] int8; sc: [N] fp32 row absmax
+  float thr;
 };
 
 #define LGA_DPPI(v, ctrl) __builtin_amdgcn_update_dpp(0, v, ctrl, 0xF, 0xF, false)
@@ -62,8 +53,9 @@ __device__ __forceinline__ int butterfly_i(int* a, int lane) {
 }
 
 template <int RPR, bool DUAL, bool NORM, bool RES, int XPT, int CPT, bool MULTI>
-__global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
+__global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args ia) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const GemvPassArgs& a = ia.g;
   const int K = a.K;
   uint4* xq = (uint4*)smem;                                       // K int8: the quantized row
   uint4* xb = (uint4*)(smem + (size_t)K);                         // K bf16: the row itself (outlier columns)
@@ -77,17 +69,11 @@ __global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
   const int n8 = K / 8, n16 = K / 16;
   const int passes = MULTI ? (n16 + PASSC - 1) / PASSC : 1;
   const int row0 = (blockIdx.x * 4 + wave) * RPR;
-  const int8_t* wm[2] = {a.w, DUAL ? a.w2 : a.w};
-  const float* sm[2] = {a.sw, DUAL ? a.sw2 : a.sw};
+  const float* sm[2] = {(const float*)a.sc, (const float*)(DUAL ? a.sc2 : a.sc)};
 
-  // 1. activation (and norm weight) share of this thread: uint4 t, t+256, ... (clamped, branch-free)
+  // 1. activation (and norm weight) share of this thread
   uint4 xr[XPT], nr[XPT];
-#pragma unroll
-  for (int i = 0; i < XPT; ++i) {
-    const int u = min(t + 256 * i, n8 - 1);
-    xr[i] = ((const uint4*)a.x)[u];
-    if (NORM) nr[i] = ((const uint4*)a.norm_w)[u];
-  }
+  fetch_x<NORM>(a.x, a.norm_w, t, n8, xr, nr);
   // row scales of this wave's rows (tiny, ahead of the weight stream so no later wait drains it)
   float sws[RB];
 #pragma unroll
@@ -98,21 +84,9 @@ __global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
     for (int m = 0; m < NM; ++m) sws[i * NM + m] = sm[m][min(row0 + i, a.N - 1)];
   // 2. pass-0 weight loads of every row of this wave (rows past N re-read row N-1; never stored)
   static_assert(R >= 1 && R <= 8, "row partials per lane");
-  uint4 wa[NM][RPR][CPT];
-  uint4 wb[NM][MULTI ? RPR : 1][MULTI ? CPT : 1];
-  auto issue = [&](auto& buf, int pass) {
-#pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-      const int c = min(pass * PASSC + lane + 64 * j, n16 - 1);
-#pragma unroll
-      for (int i = 0; i < RPR; ++i)
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-          const size_t n = (size_t)min(row0 + i, a.N - 1);
-          buf[m][i][j] = ld_nt16(wm[m] + n * K + (size_t)c * 16);
-        }
-    }
-  };
+  PassBuf<NM, RPR, CPT, 0> wa;
+  PassBuf<NM, MULTI ? RPR : 1, MULTI ? CPT : 1, 0> wb;
+  auto issue = [&](auto& buf, int pass) { issue_codes<16>(buf, a, row0, lane, pass); };
   issue(wa, 0);
   uint32_t res = 0;
   if (RES) res = a.residual[min(row0 + (lane & (RPR - 1)), a.N - 1)];
@@ -121,41 +95,21 @@ __global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
   // 3. RMSNorm (optional), outlier columns and s_x, then the int8 image of x into LDS while the weights stream
   float rs = 1.0f;
   if (NORM) {
-    float ss = 0.0f;
-#pragma unroll
-    for (int i = 0; i < XPT; ++i) {
-      const bool ok = t + 256 * i < n8;
-      const uint32_t d[4] = {xr[i].x, xr[i].y, xr[i].z, xr[i].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float lo = ok ? bflo(d[q]) : 0.0f, hi = ok ? bfhi(d[q]) : 0.0f;
-        ss = fmaf(lo, lo, ss);
-        ss = fmaf(hi, hi, ss);
-      }
-    }
-    ss = wave_sum_uniform(ss);
-    if (lane == 0) red[wave] = ss;
+    rms_wave(sum_squares(xr, t, n8), red, wave, lane);
     __syncthreads();
-    rs = 1.0f / sqrtf(((red[0] + red[1]) + (red[2] + red[3])) / (float)K + a.eps);
+    rs = rms_block(red, K, a.eps);
   }
   float amax = 0.0f;
   uint64_t obits = 0;  // 8 outlier bits per uint4 of this thread
 #pragma unroll
   for (int i = 0; i < XPT; ++i) {
     const bool ok = t + 256 * i < n8;
-    uint32_t d[4] = {xr[i].x, xr[i].y, xr[i].z, xr[i].w};
-    if (NORM) {  // bf16(w * (x * rs)), two elements per instruction
-      const uint32_t nw[4] = {nr[i].x, nr[i].y, nr[i].z, nr[i].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        d[q] = pack2(__fmul_rn(bflo(nw[q]), __fmul_rn(bflo(d[q]), rs)),
-                     __fmul_rn(bfhi(nw[q]), __fmul_rn(bfhi(d[q]), rs)));
-      xr[i] = make_uint4(d[0], d[1], d[2], d[3]);
-    }
+    if (NORM) xr[i] = normalise<true>(xr[i], nr[i], rs);
+    const uint32_t d[4] = {xr[i].x, xr[i].y, xr[i].z, xr[i].w};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float lo = fabsf(bflo(d[q])), hi = fabsf(bfhi(d[q]));
-      const bool olo = ok && a.thr > 0.0f && lo >= a.thr, ohi = ok && a.thr > 0.0f && hi >= a.thr;
+      const bool olo = ok && ia.thr > 0.0f && lo >= ia.thr, ohi = ok && ia.thr > 0.0f && hi >= ia.thr;
       obits |= (uint64_t)(olo ? 1u : 0u) << (8 * i + 2 * q);
       obits |= (uint64_t)(ohi ? 1u : 0u) << (8 * i + 2 * q + 1);
       amax = fmaxf(amax, (ok && !olo) ? lo : 0.0f);
@@ -213,7 +167,7 @@ __global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
       for (int i = 0; i < RPR; ++i)
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
-          const uint4 wv = buf[m][i][j];
+          const uint4 wv = buf.w[m][i][j];
           int d = __builtin_amdgcn_sdot4((int)wv.x, (int)xv.x, 0, false);
           d = __builtin_amdgcn_sdot4((int)wv.y, (int)xv.y, d, false);
           d = __builtin_amdgcn_sdot4((int)wv.z, (int)xv.z, d, false);
@@ -233,7 +187,7 @@ __global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
           for (int i = 0; i < RPR; ++i)
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
-              const uint4 wv = buf[m][i][j];
+              const uint4 wv = buf.w[m][i][j];
               const uint32_t ww[4] = {wv.x, wv.y, wv.z, wv.w};
               const float s127 = mul_rn(sws[i * NM + m], 1.0f / 127.0f);
               float o = outp[i * NM + m];
@@ -245,18 +199,7 @@ __global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
       }
     }
   };
-  if constexpr (MULTI) {
-    for (int p = 0; p < passes; p += 2) {
-      if (p + 1 < passes) issue(wb, p + 1);
-      consume(wa, p);
-      if (p + 1 < passes) {
-        if (p + 2 < passes) issue(wa, p + 2);
-        consume(wb, p + 1);
-      }
-    }
-  } else {
-    consume(wa, 0);
-  }
+  pass_loop<MULTI>(passes, wa, wb, issue, consume);
 
   // 5. one integer butterfly for all rows of the wave; the outlier partials only when the row has outliers
   const int vi = bfly_index<RB>(lane);  // value index held by this lane
@@ -295,26 +238,17 @@ __global__ void __launch_bounds__(256) gemv_int8_kernel(GemvI8Args a) {
 }
 
 template <int RPR, bool DUAL, int XPT, int CPT, bool MULTI>
-static void launch_i8(const GemvI8Args& a, hipStream_t stream) {
-  const int waves = (a.N + RPR - 1) / RPR;
-  const dim3 blocks((waves + 3) / 4);
-  const size_t lds = (size_t)a.K * 3 + ((a.K / 8 + 15) & ~15) + 12 * 4;
-  const bool norm = a.norm_w != nullptr, res = a.residual != nullptr;
-  if (DUAL) {
-    if (norm) gemv_int8_kernel<RPR, DUAL, true, false, XPT, CPT, MULTI><<<blocks, 256, lds, stream>>>(a);
-    else gemv_int8_kernel<RPR, DUAL, false, false, XPT, CPT, MULTI><<<blocks, 256, lds, stream>>>(a);
-  } else if (norm) {
-    if (res) gemv_int8_kernel<RPR, DUAL, true, true, XPT, CPT, MULTI><<<blocks, 256, lds, stream>>>(a);
-    else gemv_int8_kernel<RPR, DUAL, true, false, XPT, CPT, MULTI><<<blocks, 256, lds, stream>>>(a);
-  } else {
-    if (res) gemv_int8_kernel<RPR, DUAL, false, true, XPT, CPT, MULTI><<<blocks, 256, lds, stream>>>(a);
-    else gemv_int8_kernel<RPR, DUAL, false, false, XPT, CPT, MULTI><<<blocks, 256, lds, stream>>>(a);
-  }
+static void launch_i8(const GemvI8Args& ia, hipStream_t stream) {
+  const size_t lds = (size_t)ia.g.K * 3 + ((ia.g.K / 8 + 15) & ~15) + 12 * 4;
+  gemv_launch<RPR, DUAL, true>(ia.g, [&](auto norm, auto res, dim3 blocks) {
+    gemv_int8_kernel<RPR, DUAL, decltype(norm)::value, decltype(res)::value, XPT, CPT, MULTI>
+        <<<blocks, 256, lds, stream>>>(ia);
+  });
 }
 
 template <bool DUAL>
 static int dispatch_i8(const GemvI8Args& a, hipStream_t stream) {
-  const int n16 = a.K / 16;
+  const int n16 = a.g.K / 16;
   // the same 16-B loads in flight per wave as the bf16 kernel: K <= 4096 4 chunks x 4 rows (fc_1 || fc_2: 2 rows of
   // each), K <= 8192 8 chunks x 2 rows, longer rows double-buffered passes of 4096 columns x 2 rows
   if (n16 <= 256) {
@@ -341,12 +275,9 @@ static int dispatch_i8(const GemvI8Args& a, hipStream_t stream) {
 extern "C" int lga_int8_gemv(const void* x, const void* qweight, const float* scales, const void* bias,
                              const void* residual, const void* norm_weight, float norm_eps, float threshold, void* y,
                              int N, int K, hipStream_t stream) {
-  LGA_CHECK_ARG(x && qweight && scales && y, "lga_int8_gemv: null pointer");
-  LGA_CHECK_ARG(N > 0 && K > 0 && K % 16 == 0, "lga_int8_gemv: K must be a positive multiple of 16");
-  LGA_CHECK_ARG(((uintptr_t)x | (uintptr_t)qweight | (uintptr_t)(norm_weight ? norm_weight : x)) % 16 == 0,
-                "lga_int8_gemv: x, qweight and norm_weight must be 16-B aligned");
-  lga::GemvI8Args a{(const uint16_t*)x, (const int8_t*)qweight, nullptr, scales, nullptr, (const uint16_t*)bias,
-                    (const uint16_t*)residual, (const uint16_t*)norm_weight, (uint16_t*)y, N, K, norm_eps, threshold};
+  LGA_GEMV_CHECKS("lga_int8_gemv", 16, x && qweight && scales && y, , (uintptr_t)x | (uintptr_t)qweight, "x, qweight");
+  lga::GemvI8Args a{{(const uint16_t*)x, (const uint8_t*)qweight, nullptr, scales, nullptr, (const uint16_t*)bias,
+                     (const uint16_t*)residual, (const uint16_t*)norm_weight, (uint16_t*)y, N, K, norm_eps}, threshold};
   const int rc = lga::dispatch_i8<false>(a, stream);
   if (rc) return rc;
   LGA_LAUNCH_RETURN();
@@ -355,13 +286,10 @@ extern "C" int lga_int8_gemv(const void* x, const void* qweight, const float* sc
 extern "C" int lga_int8_gemv_swiglu(const void* x, const void* qweight1, const float* scales1, const void* qweight2,
                                     const float* scales2, const void* norm_weight, float norm_eps, float threshold,
                                     void* y, int N, int K, hipStream_t stream) {
-  LGA_CHECK_ARG(x && qweight1 && scales1 && qweight2 && scales2 && y, "lga_int8_gemv_swiglu: null pointer");
-  LGA_CHECK_ARG(N > 0 && K > 0 && K % 16 == 0, "lga_int8_gemv_swiglu: K must be a positive multiple of 16");
-  LGA_CHECK_ARG(((uintptr_t)x | (uintptr_t)qweight1 | (uintptr_t)qweight2 |
-                 (uintptr_t)(norm_weight ? norm_weight : x)) % 16 == 0,
-                "lga_int8_gemv_swiglu: x, qweights and norm_weight must be 16-B aligned");
-  lga::GemvI8Args a{(const uint16_t*)x, (const int8_t*)qweight1, (const int8_t*)qweight2, scales1, scales2, nullptr,
-                    nullptr, (const uint16_t*)norm_weight, (uint16_t*)y, N, K, norm_eps, threshold};
+  LGA_GEMV_CHECKS("lga_int8_gemv_swiglu", 16, x && qweight1 && scales1 && qweight2 && scales2 && y, ,
+                  (uintptr_t)x | (uintptr_t)qweight1 | (uintptr_t)qweight2, "x, qweights");
+  lga::GemvI8Args a{{(const uint16_t*)x, (const uint8_t*)qweight1, (const uint8_t*)qweight2, scales1, scales2, nullptr,
+                     nullptr, (const uint16_t*)norm_weight, (uint16_t*)y, N, K, norm_eps}, threshold};
   const int rc = lga::dispatch_i8<true>(a, stream);
   if (rc) return rc;
   LGA_LAUNCH_RETURN();

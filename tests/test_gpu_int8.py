@@ -18,7 +18,7 @@ from oracle import synth
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
-GEMV_SHAPES = [(1000, 256), (77, 1376), (640, 4096), (4096, 11008)]
+GEMV_SHAPES = [(1000, 256), (77, 1376), (640, 4096), (4096, 11008), (6, 8192), (5, 16384)]
 
 
 @pytest.fixture(scope="module")

@@ -220,9 +220,9 @@ def test_bf16_gemv_matches_reference(ops, N, K):
     assert np.all(np.abs(y - ref) <= tol), float(np.max(np.abs(y - ref) - tol))
 
 
-@pytest.mark.parametrize("K", [1024, 11008])
+@pytest.mark.parametrize("K", [1024, 11008, 16384])
 def test_bf16_gemv_fused_norm_residual_bias(ops, K):
-    N = 1536
+    N = 6 if K == 16384 else 1536  # (the K > 12288 class, 16 uint4 of x per thread with the norm, at a small N)
     w = bf16_np(_weights(N, K, "bgvf"))
     x = bf16_np(synth.normal((K,), "bxf", 5, 2.0))
     nw = bf16_np(1.0 + synth.normal((K,), "bnw", 5, 0.2))
@@ -236,7 +236,7 @@ def test_bf16_gemv_fused_norm_residual_bias(ops, K):
     assert np.max(np.abs(y - ref) - np.abs(ref) * 2 ** -7 - np.abs(h) * 2 ** -7) <= 2e-3
 
 
-@pytest.mark.parametrize("N,K", [(11008, 4096), (333, 8192)])
+@pytest.mark.parametrize("N,K", [(11008, 4096), (333, 8192), (6, 16384)])
 def test_bf16_gemv_swiglu(ops, N, K):
     w1, w2 = bf16_np(_weights(N, K, "bs1")), bf16_np(_weights(N, K, "bs2"))
     x = bf16_np(synth.normal((K,), "bxs", 5, 1.0))
