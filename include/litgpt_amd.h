@@ -204,6 +204,20 @@ int lga_mxfp4_gemv_swiglu(const void* x, const uint8_t* codes1, const uint8_t* s
 int lga_mxfp4_gemm(const void* x, const uint8_t* codes, const uint8_t* scales, const void* bias, const void* residual,
                    void* y, int M, int N, int K, lga_stream_t stream);
 
+/* -- mxfp4-a8: the mxfp4 weights above under MXFP8 activations on the block-scaled MFMA (csrc/gemm_mxfp4_a8.hip) -----
+ * mx8(X), X [M][K] bf16, per block of 32 consecutive columns of a row (the fp8 KV cache's rule on blocks of 32):
+ * s = 2^e the smallest power of two with amax / s <= 448, e clamped to [-126, 127], amax = 0 gives s = 1;
+ * code_i = e4m3fn(x_i / s), round to nearest even, nothing saturates; code_i * s is exact in bf16. The scale is stored
+ * as the e8m0 byte e + 127 (1..254). K % 32 == 0; x, codes, xcodes and w 16-B aligned (scales: none); nothing is
+ * launched before the checks pass. */
+/* activation quantizer: x [M][K] bf16 -> codes [M][K] uint8 e4m3fn, scales [M][K / 32] uint8 e8m0; M >= 1 */
+int lga_mx8_quantize(const void* x, uint8_t* codes, uint8_t* scales, int M, int K, lga_stream_t stream);
+/* prefill GEMM Y (M, N) = (xcodes * 2^(xscales - 127)) (M, K) . W'^T [+bias] [+residual], W' = (w, wscales) as
+ * lga_mxfp4_quantize writes them, on v_mfma_scale_f32_16x16x128_f8f6f4: exact fp8 x fp4 products, fp32 accumulation,
+ * the rounding points of lga_mxfp4_gemm's epilogue; M >= 1 */
+int lga_mxfp4_a8_gemm(const uint8_t* xcodes, const uint8_t* xscales, const uint8_t* w, const uint8_t* wscales,
+                      const void* bias, const void* residual, void* y, int M, int N, int K, lga_stream_t stream);
+
 /* -- LoRA adapters (the reference's lit_gpt/lora.py: the unmerged LoRALinear / LoRAQKVLinear forward :170-177,
  *    :398-433 and LoRALinear.merge :140-149, under bf16-true) --------------------------------------------------
  * Device layout, built once when the adapter is attached: A (R, K) bf16; B (N, r) bf16 in output-row order;

@@ -159,8 +159,9 @@ __global__ void __launch_bounds__(256) gemm_mxfp4_kernel(GemmMx4Args a) {
 }
 
 int preload_mxfp4_gemv();
+int preload_mxfp4_a8();
 int preload_mxfp4() {
-  return preload(gemm_mxfp4_kernel<2>) + preload(gemm_mxfp4_kernel<4>) + preload_mxfp4_gemv();
+  return preload(gemm_mxfp4_kernel<2>) + preload(gemm_mxfp4_kernel<4>) + preload_mxfp4_gemv() + preload_mxfp4_a8();
 }
 
 }  // namespace lga

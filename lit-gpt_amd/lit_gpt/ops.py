@@ -72,6 +72,8 @@ SIGNATURES = {
     "lga_mxfp4_gemv": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
     "lga_mxfp4_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
     "lga_mxfp4_gemm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "lga_mx8_quantize": [_P, _P, _P, _I, _I, _P],
+    "lga_mxfp4_a8_gemm": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_lora_gemv": [_P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_lora_gemv_rows": [_P, _P, _F, _P, _P, _P, _P, _I, ctypes.c_longlong, ctypes.c_longlong, _F, _P, _P, _P, _I,
                            _I, _I, _I, _I, _P],
@@ -648,6 +650,39 @@ def mxfp4_gemm(x, codes, scales, *, bias=None, residual=None, out=None):
                                          _dev(scales, "scales", torch.uint8), _opt(bias, "bias", torch.bfloat16),
                                          _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
                                          M, N, K, _stream()))
+    return y
+
+
+def mx8_quantize(x: torch.Tensor, out=None):
+    """(M, K) bf16 device activations -> (e4m3fn codes uint8 (M, K), e8m0 scale bytes uint8 (M, K / 32)): MXFP8, the
+    fp8 KV cache's scale rule on every 32 consecutive columns of a row (include/litgpt_amd.h). ``out``: the pair to
+    write into."""
+    M, K = x.shape
+    if K % MXFP4_GROUP:
+        raise ValueError(f"mx8_quantize: K={K} is not a multiple of {MXFP4_GROUP}")
+    codes, scales = out if out is not None else (torch.empty(M, K, dtype=torch.uint8, device=x.device),
+                                                 torch.empty(M, K // MXFP4_GROUP, dtype=torch.uint8, device=x.device))
+    if codes.shape != (M, K) or scales.shape != (M, K // MXFP4_GROUP):
+        raise ValueError(f"mx8_quantize: out shapes {tuple(codes.shape)}, {tuple(scales.shape)} for x {tuple(x.shape)}")
+    _check(load_library().lga_mx8_quantize(_dev(x, "x", torch.bfloat16), _dev(codes, "codes", torch.uint8),
+                                           _dev(scales, "scales", torch.uint8), M, K, _stream()))
+    return codes, scales
+
+
+def mxfp4_a8_gemm(xcodes, xscales, codes, scales, *, bias=None, residual=None, out=None):
+    """Y (M, N) = mx8 activations (xcodes, xscales) . W'^T [+bias] [+residual] on the block-scaled fp8 x fp4 MFMA, W'
+    the mxfp4 weight (codes, scales)."""
+    M = xcodes.shape[0]
+    N, K = codes.shape[0], codes.shape[1] * 2
+    if xcodes.shape[1] != K or xscales.shape != (M, K // MXFP4_GROUP) or scales.shape != (N, K // MXFP4_GROUP):
+        raise ValueError(f"mxfp4_a8_gemm: shapes xcodes {tuple(xcodes.shape)} xscales {tuple(xscales.shape)} codes "
+                         f"{tuple(codes.shape)} scales {tuple(scales.shape)}")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=xcodes.device)
+    _check(load_library().lga_mxfp4_a8_gemm(_dev(xcodes, "xcodes", torch.uint8), _dev(xscales, "xscales", torch.uint8),
+                                            _dev(codes, "codes", torch.uint8), _dev(scales, "scales", torch.uint8),
+                                            _opt(bias, "bias", torch.bfloat16),
+                                            _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
+                                            M, N, K, _stream()))
     return y
 
 

@@ -1,5 +1,5 @@
 """Quantized Linears — the drop-ins for bitsandbytes' ``Linear4bit`` (4-bit weight-only) and ``Linear8bitLt``
-(``bnb.int8``, LLM.int8), the weight-only fp8 and MXFP4 Linears (``fp8-g128``, ``mxfp4``) — and how a Linear of each
+(``bnb.int8``, LLM.int8), the weight-only fp8 and MXFP4 Linears (``fp8-g128``, ``mxfp4``, ``mxfp4-a8``) — and how a Linear of each
 weight format (4-bit, int8, fp8, mxfp4, bf16, fp32) runs on the kernels
 (``_Kernels``, ``kernels``, ``swiglu``).
 
@@ -34,6 +34,10 @@ Modes:
                                               one e8m0 power-of-two scale per 32 weights of a row (MX v1.0 §6.3);
                                               4.25 bits per weight, the dequantized weight exact in bf16, bf16
                                               activations. in_features must be a multiple of 32
+  "mxfp4-a8"                                  mxfp4's weights, byte for byte (``Mxfp4A8Linear``); activations are
+                                              rounded to MXFP8 (e4m3 codes, one e8m0 scale per 32 columns) where the
+                                              Linear is compute-bound (M >= 2: prefill, scoring), for the block-scaled
+                                              fp8 x fp4 MFMA, and stay bf16 on the one-row decode step
 Group sizes must divide in_features; for a TP row-shard whose width is not a multiple of the requested group
 (e.g. Llama-2-7B mlp.proj at TP=8: 1376) the largest of {128, 64, 32} that divides it is used.
 """
@@ -78,6 +82,7 @@ _MODES = {
     "bnb.int8": (ops.FMT_INT8, 0),  # Int8Linear: one fp32 scale per row, no group
     "fp8-g128": (ops.FMT_FP8, 128),  # Fp8Linear: e4m3 codes, one power-of-two bf16 scale per 128 weights
     "mxfp4": (ops.FMT_MXFP4, 32),  # Mxfp4Linear: e2m1 codes, one e8m0 scale byte per 32 weights
+    "mxfp4-a8": (ops.FMT_MXFP4, 32),  # Mxfp4A8Linear: the same weights; M >= 2 rounds the activations to MXFP8
 }
 
 
@@ -428,6 +433,25 @@ class Mxfp4Linear(_Kernels, nn.Module):
                 f"e8m0 block={ops.MXFP4_GROUP}")
 
 
+class Mxfp4A8Linear(Mxfp4Linear):
+    """``mxfp4-a8``: an ``Mxfp4Linear`` (same quantizer, buffers and bytes: a checkpoint converted under one mode loads
+    under the other) whose several-row product runs on the block-scaled fp8 x fp4 MFMA. Activations are rounded to
+    MXFP8 where the Linear is compute-bound (M >= 2: ``lga_mx8_quantize`` then ``lga_mxfp4_a8_gemm``) and stay bf16 on
+    the one-row decode step (the inherited GEMVs, bit for bit what ``mxfp4`` gives)."""
+
+    _act_ws: dict = {}  # (M, K, device) -> (codes, scales) of the quantized activations, shared by every Linear
+
+    def gemm(self, x, res):
+        key = (x.shape[0], self.in_features, x.device)
+        ws = self._act_ws.get(key)
+        if ws is None:  # allocated at the first call of a shape, so a captured prefill sees no allocation
+            ws = self._act_ws[key] = (torch.empty(key[0], key[1], dtype=torch.uint8, device=x.device),
+                                      torch.empty(key[0], key[1] // ops.MXFP4_GROUP, dtype=torch.uint8,
+                                                  device=x.device))
+        xc, xs = ops.mx8_quantize(x, out=ws)
+        return ops.mxfp4_a8_gemm(xc, xs, self.qweight, self.scales, bias=self.bias, residual=res)
+
+
 class _DenseLinear(_Kernels):
     """The per-call adapter of a device ``nn.Linear`` (bf16 or fp32 weights) to the ``_Kernels`` skeleton."""
 
@@ -504,7 +528,7 @@ def kernels(lin: nn.Module) -> _Kernels:
         return (F32Linear if lin.weight.dtype == torch.float32 else Bf16Linear)(lin)
     raise NotImplementedError(
         "Linear without MI355X weights: move the model to the GPU in bf16, or convert it with "
-        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8' | 'fp8-g128' | 'mxfp4')"
+        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8' | 'fp8-g128' | 'mxfp4' | 'mxfp4-a8')"
         ".convert_module(model) (the --quantize "
         "flag)")
 
@@ -558,10 +582,12 @@ class QuantizedPrecision:
 
     def convert_module(self, module: nn.Module, device: Optional[torch.device] = None) -> nn.Module:
         """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` (``Int8Linear`` for ``bnb.int8``,
-        ``Fp8Linear`` for ``fp8-g128``, ``Mxfp4Linear`` for ``mxfp4``) quantized on ``device``."""
+        ``Fp8Linear`` for ``fp8-g128``, ``Mxfp4Linear`` for ``mxfp4``, ``Mxfp4A8Linear`` for ``mxfp4-a8``) quantized on
+        ``device``."""
         for name, child in list(module.named_children()):
             if isinstance(child, nn.Linear):
-                cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear, "mxfp4": Mxfp4Linear}.get(self.mode, QuantLinear)
+                cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear, "mxfp4": Mxfp4Linear,
+                       "mxfp4-a8": Mxfp4A8Linear}.get(self.mode, QuantLinear)
                 setattr(module, name, cls.from_float(child.weight, child.bias, mode=self.mode, device=device))
             else:
                 self.convert_module(child, device)
