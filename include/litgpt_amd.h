@@ -218,6 +218,15 @@ int lga_mx8_quantize(const void* x, uint8_t* codes, uint8_t* scales, int M, int 
 int lga_mxfp4_a8_gemm(const uint8_t* xcodes, const uint8_t* xscales, const uint8_t* w, const uint8_t* wscales,
                       const void* bias, const void* residual, void* y, int M, int N, int K, lga_stream_t stream);
 
+/* -- fp8-g128-a8: the fp8-g128 weights above under MXFP8 activations on the block-scaled MFMA (csrc/gemm_fp8_a8.hip) --
+ * prefill GEMM Y (M, N) = (xcodes * 2^(xscales - 127)) (M, K) . W'^T [+bias] [+residual]: xcodes / xscales as
+ * lga_mx8_quantize writes them, W' = (codes, scales) as lga_fp8_quantize writes them (scales bf16 powers of two 2^e, e
+ * in [-126, 127]; the kernel passes the e8m0 byte (bits >> 7) & 0xFF). v_mfma_scale_f32_16x16x128_f8f6f4 with both
+ * operands e4m3: exact fp8 x fp8 products, fp32 accumulation, the rounding points of lga_fp8_gemm's epilogue. M >= 1,
+ * N > 0, K % 128 == 0; xcodes and codes 16-B aligned; nothing is launched before the checks pass. */
+int lga_fp8_a8_gemm(const uint8_t* xcodes, const uint8_t* xscales, const uint8_t* codes, const void* scales,
+                    const void* bias, const void* residual, void* y, int M, int N, int K, lga_stream_t stream);
+
 /* -- LoRA adapters (the reference's lit_gpt/lora.py: the unmerged LoRALinear / LoRAQKVLinear forward :170-177,
  *    :398-433 and LoRALinear.merge :140-149, under bf16-true) --------------------------------------------------
  * Device layout, built once when the adapter is attached: A (R, K) bf16; B (N, r) bf16 in output-row order;

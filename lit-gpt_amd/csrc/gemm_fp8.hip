@@ -138,8 +138,9 @@ __global__ void __launch_bounds__(256) gemm_fp8_kernel(GemmF8Args a) {
 }
 
 int preload_fp8_gemv();
+int preload_fp8_a8();
 int preload_fp8() {
-  return preload(gemm_fp8_kernel<2>) + preload(gemm_fp8_kernel<4>) + preload_fp8_gemv();
+  return preload(gemm_fp8_kernel<2>) + preload(gemm_fp8_kernel<4>) + preload_fp8_gemv() + preload_fp8_a8();
 }
 
 }  // namespace lga

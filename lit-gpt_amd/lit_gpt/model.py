@@ -158,8 +158,8 @@ class GPT(nn.Module):
         the batch) counts as its base Linear; a single-adapter ``LoraLinear`` stays refused."""
         from lit_gpt.lora import MultiLoraLinear  # (lit_gpt.lora imports this package)
 
-        def four_bit(lin, name):  # ... or fp8-g128: the formats with a rows GEMV
-            plain = (quantize.QuantLinear, quantize.Fp8Linear)
+        def four_bit(lin, name):  # ... or fp8-g128 / fp8-g128-a8 (the same GEMVs): the formats with a rows GEMV
+            plain = (quantize.QuantLinear, quantize.Fp8Linear, quantize.Fp8A8Linear)
             if adapters and isinstance(lin, MultiLoraLinear) and not lin._forward_hooks:
                 lin, plain = lin.base, (quantize.QuantLinear,)  # several adapters: over a 4-bit base only
             if type(lin) not in plain or lin._forward_hooks:

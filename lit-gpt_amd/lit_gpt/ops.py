@@ -74,6 +74,7 @@ SIGNATURES = {
     "lga_mxfp4_gemm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_mx8_quantize": [_P, _P, _P, _I, _I, _P],
     "lga_mxfp4_a8_gemm": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "lga_fp8_a8_gemm": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_lora_gemv": [_P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _I, _I, _I, _I, _P],
     "lga_lora_gemv_rows": [_P, _P, _F, _P, _P, _P, _P, _I, ctypes.c_longlong, ctypes.c_longlong, _F, _P, _P, _P, _I,
                            _I, _I, _I, _I, _P],
@@ -683,6 +684,24 @@ def mxfp4_a8_gemm(xcodes, xscales, codes, scales, *, bias=None, residual=None, o
                                             _opt(bias, "bias", torch.bfloat16),
                                             _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
                                             M, N, K, _stream()))
+    return y
+
+
+def fp8_a8_gemm(xcodes, xscales, codes, scales, *, bias=None, residual=None, out=None):
+    """Y (M, N) = mx8 activations (xcodes, xscales) . W'^T [+bias] [+residual] on the block-scaled fp8 x fp8 MFMA, W'
+    the fp8-g128 weight (codes, scales)."""
+    M = xcodes.shape[0]
+    N, K = codes.shape
+    if (K % FP8_GROUP or xcodes.shape[1] != K or xscales.shape != (M, K // MXFP4_GROUP)
+            or scales.shape != (N, K // FP8_GROUP)):
+        raise ValueError(f"fp8_a8_gemm: shapes xcodes {tuple(xcodes.shape)} xscales {tuple(xscales.shape)} codes "
+                         f"{tuple(codes.shape)} scales {tuple(scales.shape)}")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=xcodes.device)
+    _check(load_library().lga_fp8_a8_gemm(_dev(xcodes, "xcodes", torch.uint8), _dev(xscales, "xscales", torch.uint8),
+                                          _dev(codes, "codes", torch.uint8), _dev(scales, "scales", torch.bfloat16),
+                                          _opt(bias, "bias", torch.bfloat16),
+                                          _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
+                                          M, N, K, _stream()))
     return y
 
 

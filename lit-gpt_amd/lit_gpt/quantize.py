@@ -1,5 +1,5 @@
 """Quantized Linears — the drop-ins for bitsandbytes' ``Linear4bit`` (4-bit weight-only) and ``Linear8bitLt``
-(``bnb.int8``, LLM.int8), the weight-only fp8 and MXFP4 Linears (``fp8-g128``, ``mxfp4``, ``mxfp4-a8``) — and how a Linear of each
+(``bnb.int8``, LLM.int8), the fp8 and MXFP4 Linears (``fp8-g128``, ``fp8-g128-a8``, ``mxfp4``, ``mxfp4-a8``) — and how a Linear of each
 weight format (4-bit, int8, fp8, mxfp4, bf16, fp32) runs on the kernels
 (``_Kernels``, ``kernels``, ``swiglu``).
 
@@ -38,6 +38,10 @@ Modes:
                                               rounded to MXFP8 (e4m3 codes, one e8m0 scale per 32 columns) where the
                                               Linear is compute-bound (M >= 2: prefill, scoring), for the block-scaled
                                               fp8 x fp4 MFMA, and stay bf16 on the one-row decode step
+  "fp8-g128-a8"                               fp8-g128's weights, byte for byte (``Fp8A8Linear``); activations are
+                                              rounded to MXFP8 where the Linear is compute-bound (the GEMM at M >= 2:
+                                              prefill, scoring), for the block-scaled fp8 x fp8 MFMA, and stay bf16
+                                              on the one-row and multi-row decode GEMVs
 Group sizes must divide in_features; for a TP row-shard whose width is not a multiple of the requested group
 (e.g. Llama-2-7B mlp.proj at TP=8: 1376) the largest of {128, 64, 32} that divides it is used.
 """
@@ -83,6 +87,7 @@ _MODES = {
     "fp8-g128": (ops.FMT_FP8, 128),  # Fp8Linear: e4m3 codes, one power-of-two bf16 scale per 128 weights
     "mxfp4": (ops.FMT_MXFP4, 32),  # Mxfp4Linear: e2m1 codes, one e8m0 scale byte per 32 weights
     "mxfp4-a8": (ops.FMT_MXFP4, 32),  # Mxfp4A8Linear: the same weights; M >= 2 rounds the activations to MXFP8
+    "fp8-g128-a8": (ops.FMT_FP8, 128),  # Fp8A8Linear: fp8-g128's weights; the GEMM rounds the activations to MXFP8
 }
 
 
@@ -439,17 +444,35 @@ class Mxfp4A8Linear(Mxfp4Linear):
     MXFP8 where the Linear is compute-bound (M >= 2: ``lga_mx8_quantize`` then ``lga_mxfp4_a8_gemm``) and stay bf16 on
     the one-row decode step (the inherited GEMVs, bit for bit what ``mxfp4`` gives)."""
 
-    _act_ws: dict = {}  # (M, K, device) -> (codes, scales) of the quantized activations, shared by every Linear
+    def gemm(self, x, res):
+        xc, xs = ops.mx8_quantize(x, out=_mx8_workspace(x, self.in_features))
+        return ops.mxfp4_a8_gemm(xc, xs, self.qweight, self.scales, bias=self.bias, residual=res)
+
+
+class Fp8A8Linear(Fp8Linear):
+    """``fp8-g128-a8``: an ``Fp8Linear`` (same quantizer, buffers and bytes: a checkpoint converted under one mode loads
+    under the other) whose several-row product runs on the block-scaled fp8 x fp8 MFMA. Activations are rounded to
+    MXFP8 where the Linear is compute-bound (M >= 2 through ``gemm``: ``lga_mx8_quantize`` then ``lga_fp8_a8_gemm``) and
+    stay bf16 on the one-row decode step and the multi-row decode GEMVs (inherited, bit for bit what ``fp8-g128``
+    gives)."""
 
     def gemm(self, x, res):
-        key = (x.shape[0], self.in_features, x.device)
-        ws = self._act_ws.get(key)
-        if ws is None:  # allocated at the first call of a shape, so a captured prefill sees no allocation
-            ws = self._act_ws[key] = (torch.empty(key[0], key[1], dtype=torch.uint8, device=x.device),
-                                      torch.empty(key[0], key[1] // ops.MXFP4_GROUP, dtype=torch.uint8,
-                                                  device=x.device))
-        xc, xs = ops.mx8_quantize(x, out=ws)
-        return ops.mxfp4_a8_gemm(xc, xs, self.qweight, self.scales, bias=self.bias, residual=res)
+        xc, xs = ops.mx8_quantize(x, out=_mx8_workspace(x, self.in_features))
+        return ops.fp8_a8_gemm(xc, xs, self.qweight, self.scales, bias=self.bias, residual=res)
+
+
+_MX8_WS: dict = {}  # (M, K, device) -> (codes, scales) of the quantized activations, shared by every -a8 Linear
+
+
+def _mx8_workspace(x: torch.Tensor, K: int):
+    """The MXFP8 image of (M, K) activations on x's device: allocated at the first call of a shape, so a captured
+    prefill sees no allocation."""
+    key = (x.shape[0], K, x.device)
+    ws = _MX8_WS.get(key)
+    if ws is None:
+        ws = _MX8_WS[key] = (torch.empty(key[0], K, dtype=torch.uint8, device=x.device),
+                             torch.empty(key[0], K // ops.MXFP4_GROUP, dtype=torch.uint8, device=x.device))
+    return ws
 
 
 class _DenseLinear(_Kernels):
@@ -528,7 +551,8 @@ def kernels(lin: nn.Module) -> _Kernels:
         return (F32Linear if lin.weight.dtype == torch.float32 else Bf16Linear)(lin)
     raise NotImplementedError(
         "Linear without MI355X weights: move the model to the GPU in bf16, or convert it with "
-        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8' | 'fp8-g128' | 'mxfp4' | 'mxfp4-a8')"
+        "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8' | 'fp8-g128' | 'fp8-g128-a8' | 'mxfp4' | "
+        "'mxfp4-a8')"
         ".convert_module(model) (the --quantize "
         "flag)")
 
@@ -582,12 +606,12 @@ class QuantizedPrecision:
 
     def convert_module(self, module: nn.Module, device: Optional[torch.device] = None) -> nn.Module:
         """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` (``Int8Linear`` for ``bnb.int8``,
-        ``Fp8Linear`` for ``fp8-g128``, ``Mxfp4Linear`` for ``mxfp4``, ``Mxfp4A8Linear`` for ``mxfp4-a8``) quantized on
-        ``device``."""
+        ``Fp8Linear`` for ``fp8-g128``, ``Fp8A8Linear`` for ``fp8-g128-a8``, ``Mxfp4Linear`` for ``mxfp4``,
+        ``Mxfp4A8Linear`` for ``mxfp4-a8``) quantized on ``device``."""
         for name, child in list(module.named_children()):
             if isinstance(child, nn.Linear):
-                cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear, "mxfp4": Mxfp4Linear,
-                       "mxfp4-a8": Mxfp4A8Linear}.get(self.mode, QuantLinear)
+                cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear, "fp8-g128-a8": Fp8A8Linear,
+                       "mxfp4": Mxfp4Linear, "mxfp4-a8": Mxfp4A8Linear}.get(self.mode, QuantLinear)
                 setattr(module, name, cls.from_float(child.weight, child.bias, mode=self.mode, device=device))
             else:
                 self.convert_module(child, device)
