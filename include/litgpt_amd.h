@@ -33,6 +33,7 @@ typedef struct ihipStream_t* lga_stream_t; /* == hipStream_t */
 #define LGA_FMT_INT8 4 /* LLM.int8: int8 [N][K], fp32 row absmax (the lga_int8_* entry points only) */
 #define LGA_FMT_FP8 5 /* fp8-g128: e4m3fn codes [N][K], bf16 power-of-two scale per 128 (the lga_fp8_* entry points only) */
 #define LGA_FMT_MXFP4 6 /* mxfp4: e2m1 code pairs [N][K / 2], e8m0 scale byte per 32 (the lga_mxfp4_* entry points only) */
+#define LGA_FMT_MXFP6 7 /* mxfp6: e2m3 codes [N][3 K / 4], e8m0 scale byte per 32 (the lga_mxfp6_* entry points only) */
 
 /* -- plumbing ---------------------------------------------------------------------------------------- */
 const char* lga_last_error_string(void);
@@ -202,6 +203,37 @@ int lga_mxfp4_gemv_swiglu(const void* x, const uint8_t* codes1, const uint8_t* s
 /* prefill GEMM Y (M, N) = X (M, K) . W'^T [+bias] [+residual] on the bf16 MFMA, the code tile expanded in registers;
  * M >= 2 */
 int lga_mxfp4_gemm(const void* x, const uint8_t* codes, const uint8_t* scales, const void* bias, const void* residual,
+                   void* y, int M, int N, int K, lga_stream_t stream);
+
+/* -- mxfp6: weight-only OCP MXFP6 (e2m3) Linears, bf16 activations (csrc/gemv_mxfp6.hip, csrc/gemm_mxfp6.hip) --------
+ * Element: OCP MX v1.0 e2m3, 6 bits: bit 5 sign, bits 4:3 exponent E (bias 1), bits 2:0 mantissa M; magnitude M / 8
+ * for E = 0 and 2^(E - 1) (1 + M / 8) for E = 1..3, the largest 7.5; no Inf, no NaN. Storage: codes [N][3 K / 4] uint8,
+ * a block's 32 codes in 24 consecutive bytes, code i (column i of the block) in bits 6 i .. 6 i + 5 of the block's
+ * 192-bit little-endian word — the order v_cvt_scalef32_pk32_bf16_fp6 reads from 6 consecutive dwords; scales
+ * [N][K / 32] uint8 e8m0, byte e = 2^(e - 127), one per block of 32 consecutive weights of a row. Rule (OCP MX v1.0
+ * 6.3, on fp32 values; bf16 input converts exactly): amax = max |w_i| of the block; amax = 0 gives e = 127 and all
+ * codes 0; else s = floor(log2 amax) - 2 clamped to [-123, 125], e = s + 127 in [4, 252]; code_i = w_i 2^-s rounded to
+ * the nearest e2m3 value, ties to the even code, magnitudes above 7.5 saturating to 7.5; the code's sign bit is the
+ * sign bit of w_i, also where the magnitude rounds to zero. With e >= 4 the smallest nonzero magnitude is 2^-3 2^-123:
+ * W'[n][k] = e2m3(code) * 2^(e - 127) is zero or a normal bf16 (blocks with non-finite values are outside the
+ * contract). Every entry point computes what the lga_bf16_* one computes on W':
+ * fp32 accumulation of exact bf16 x bf16 products, in an order of its own, with the same bf16 rounding points in the
+ * RMSNorm prologue and the bias / residual / SwiGLU epilogues. K % 64 == 0 everywhere (a row is a run of 48-B block
+ * pairs and starts 16-B aligned); x, codes and norm_weight 16-B aligned, the GEMVs' scales 2-B aligned; nothing is
+ * launched before the checks pass. */
+/* weight quantizer: w [N][K] fp32 (w_is_bf16 = 0) or bf16 (1) -> codes, scales */
+int lga_mxfp6_quantize(const void* w, int w_is_bf16, uint8_t* codes, uint8_t* scales, int N, int K,
+                       lga_stream_t stream);
+/* decode GEMV y (N) = x (K) . W'^T [+bias] [+residual]; K <= 32768; optional fused RMSNorm of x for K <= 12288 */
+int lga_mxfp6_gemv(const void* x, const uint8_t* codes, const uint8_t* scales, const void* bias, const void* residual,
+                   const void* norm_weight, float norm_eps, void* y, int N, int K, lga_stream_t stream);
+/* y = bf16(silu(bf16(x W1'^T))) * bf16(x W2'^T), the same K limits */
+int lga_mxfp6_gemv_swiglu(const void* x, const uint8_t* codes1, const uint8_t* scales1, const uint8_t* codes2,
+                          const uint8_t* scales2, const void* norm_weight, float norm_eps, void* y, int N, int K,
+                          lga_stream_t stream);
+/* prefill GEMM Y (M, N) = X (M, K) . W'^T [+bias] [+residual] on the bf16 MFMA, the code tile expanded in registers;
+ * M >= 2 */
+int lga_mxfp6_gemm(const void* x, const uint8_t* codes, const uint8_t* scales, const void* bias, const void* residual,
                    void* y, int M, int N, int K, lga_stream_t stream);
 
 /* -- mxfp4-a8: the mxfp4 weights above under MXFP8 activations on the block-scaled MFMA (csrc/gemm_mxfp4_a8.hip) -----

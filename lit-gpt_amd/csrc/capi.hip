@@ -19,7 +19,7 @@ extern "C" int lga_version(void) { return 1; }
 extern "C" int lga_preload_kernels(void) {
   const int bad = lga::preload_gemm_q4f() + lga::preload_attention() + lga::preload_norm_rope() +
                   lga::preload_sample() + lga::preload_gemv() + lga::preload_moe() + lga::preload_adapter() + lga::preload_fp8() +
-                  lga::preload_mxfp4();
+                  lga::preload_mxfp4() + lga::preload_mxfp6();
   if (bad) {
     lga_set_error("lga_preload_kernels: hipFuncGetAttributes failed");
     return 1;

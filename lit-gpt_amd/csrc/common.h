@@ -103,6 +103,7 @@ int preload_moe();
 int preload_adapter();
 int preload_fp8();
 int preload_mxfp4();
+int preload_mxfp6();
 
 }  // namespace lga
 

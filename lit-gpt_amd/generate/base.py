@@ -13,8 +13,8 @@ short) and ``main`` (:96-187) with the same flags and the same stderr timing lin
     the top-k set or, with ``--top_k none``, the whole vocabulary (ops.sample_nucleus; no torch fallback);
   * ``--quantize`` takes this build's formats (int4-g128, nf4 / bnb.nf4 / bnb.nf4-dq, bnb.fp4 / bnb.fp4-dq, bnb.int8,
     fp8-g128: weight-only e4m3, mxfp4: weight-only OCP MXFP4, mxfp4-a8: mxfp4 weights with MXFP8 activations at
-    M >= 2, fp8-g128-a8: fp8-g128 weights with MXFP8 activations in the prefill GEMM; all four one device, dense
-    models); without it the Linears stay bf16 ``nn.Linear`` (BASELINE config 2) and run on the bf16 GEMV / GEMM
+    M >= 2, fp8-g128-a8: fp8-g128 weights with MXFP8 activations in the prefill GEMM, mxfp6: weight-only OCP MXFP6
+    e2m3; all five one device, dense models); without it the Linears stay bf16 ``nn.Linear`` (BASELINE config 2) and run on the bf16 GEMV / GEMM
     kernels;
   * ``--synthetic NAME`` builds a random-init model of a registered config (no checkpoint, no tokenizer): the
     prompt is ``--prompt_len`` synthetic token ids.
@@ -565,7 +565,7 @@ def build_model(config: Config, *, quantize: Optional[str], device: torch.device
             if fabric is not None and fabric.world_size > 1:
                 raise NotImplementedError("--quantize bnb.int8 with tensor parallelism: the fused GEMV + all-reduce "
                                           "takes 4-bit or bf16 shards only; run bnb.int8 on one device")
-        if quantize in ("fp8-g128", "fp8-g128-a8", "mxfp4", "mxfp4-a8"):  # the same two limits, for the same reasons
+        if quantize in ("fp8-g128", "fp8-g128-a8", "mxfp4", "mxfp4-a8", "mxfp6"):  # the same two limits, for the same reasons
             if config._mlp_class == "LLaMAMoE":
                 raise NotImplementedError(f"--quantize {quantize} with a sparse-MoE model: the routed expert kernels "
                                           "take 4-bit experts only (int4-g128, nf4, bnb.fp4 and their -dq forms)")

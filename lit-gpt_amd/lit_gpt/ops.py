@@ -29,6 +29,7 @@ FMT_FP4 = 3  # bitsandbytes FP4 code, per-block fp32 absmax
 FMT_INT8 = 4  # LLM.int8: int8 (N, K) + fp32 row absmax (the int8_* ops only)
 FMT_FP8 = 5  # fp8-g128: e4m3fn codes (N, K) + bf16 power-of-two scale per 128 weights (the fp8_* ops only)
 FMT_MXFP4 = 6  # mxfp4: e2m1 code pairs (N, K / 2) + e8m0 scale byte per 32 weights (the mxfp4_* ops only)
+FMT_MXFP6 = 7  # mxfp6: e2m3 codes (N, 3 K / 4) + e8m0 scale byte per 32 weights (the mxfp6_* ops only)
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -72,6 +73,10 @@ SIGNATURES = {
     "lga_mxfp4_gemv": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
     "lga_mxfp4_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
     "lga_mxfp4_gemm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "lga_mxfp6_quantize": [_P, _I, _P, _P, _I, _I, _P],
+    "lga_mxfp6_gemv": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
+    "lga_mxfp6_gemv_swiglu": [_P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _P],
+    "lga_mxfp6_gemm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_mx8_quantize": [_P, _P, _P, _I, _I, _P],
     "lga_mxfp4_a8_gemm": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "lga_fp8_a8_gemm": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
@@ -654,6 +659,73 @@ def mxfp4_gemm(x, codes, scales, *, bias=None, residual=None, out=None):
     return y
 
 
+# ------------------------------------------------------------------------------------------------ mxfp6
+MXFP6_GROUP = 32  # weights per e8m0 scale (one OCP MX block, 24 code bytes)
+MXFP6_K_STEP = 64  # in_features granularity: rows are runs of 48-B block pairs
+MXFP6_MAX_K = 32768  # lga_mxfp6_gemv(_swiglu)
+MXFP6_NORM_MAX_K = 12288  # ... with the RMSNorm fused
+
+
+def mxfp6_quantize(weight: torch.Tensor):
+    """(N, K) fp32/bf16 device weight -> (e2m3 codes uint8 (N, 3 K / 4), 32 six-bit codes per 24 bytes, little-endian;
+    e8m0 scale bytes uint8 (N, K / 32)) by the OCP MX rule on every 32 consecutive weights of a row
+    (include/litgpt_amd.h)."""
+    N, K = weight.shape
+    if K % MXFP6_K_STEP:
+        raise ValueError(f"mxfp6: in_features={K} is not a multiple of {MXFP6_K_STEP}")
+    w = weight.contiguous()
+    if w.dtype not in (torch.float32, torch.bfloat16):
+        w = w.float()
+    codes = torch.empty(N, K // 4 * 3, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, K // MXFP6_GROUP, dtype=torch.uint8, device=w.device)
+    _check(load_library().lga_mxfp6_quantize(_dev(w, "weight"), int(w.dtype == torch.bfloat16), codes.data_ptr(),
+                                             scales.data_ptr(), N, K, _stream()))
+    return codes, scales
+
+
+def mxfp6_gemv(x, codes, scales, *, bias=None, residual=None, norm_weight=None, eps=1e-5, out=None):
+    """y (N,) = x (K,) . W'^T [+bias] [+residual] for W' = e2m3(codes) * 2^(scales - 127); optional fused RMSNorm of x
+    (K <= MXFP6_NORM_MAX_K)."""
+    N, K = codes.shape[0], codes.shape[1] // 3 * 4
+    y = out if out is not None else torch.empty(N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_mxfp6_gemv(_dev(x, "x", torch.bfloat16), _dev(codes, "codes", torch.uint8),
+                                         _dev(scales, "scales", torch.uint8), _opt(bias, "bias", torch.bfloat16),
+                                         _opt(residual, "residual", torch.bfloat16),
+                                         _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                         _dev(y, "y", torch.bfloat16), N, K, _stream()))
+    return y
+
+
+def mxfp6_gemv_swiglu(x, codes1, scales1, codes2, scales2, *, norm_weight=None, eps=1e-5, out=None):
+    """y (N,) = bf16(silu(bf16(x W1'^T))) * bf16(x W2'^T) with mxfp6 weights, optional fused RMSNorm of x."""
+    N, K = codes1.shape[0], codes1.shape[1] // 3 * 4
+    if codes2.shape != codes1.shape:
+        raise ValueError(f"mxfp6_gemv_swiglu: weight shapes differ {tuple(codes1.shape)} vs {tuple(codes2.shape)}")
+    y = out if out is not None else torch.empty(N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_mxfp6_gemv_swiglu(_dev(x, "x", torch.bfloat16), _dev(codes1, "codes1", torch.uint8),
+                                                _dev(scales1, "scales1", torch.uint8),
+                                                _dev(codes2, "codes2", torch.uint8),
+                                                _dev(scales2, "scales2", torch.uint8),
+                                                _opt(norm_weight, "norm_weight", torch.bfloat16), float(eps),
+                                                _dev(y, "y", torch.bfloat16), N, K, _stream()))
+    return y
+
+
+def mxfp6_gemm(x, codes, scales, *, bias=None, residual=None, out=None):
+    """Y (M, N) = X (M, K) . W'^T [+bias] [+residual] on the bf16 MFMA, the codes expanded in registers; M >= 2."""
+    M = x.shape[0]
+    N, K = codes.shape[0], codes.shape[1] // 3 * 4
+    if x.shape[1] != K:
+        raise ValueError(f"mxfp6_gemm: shapes x {tuple(x.shape)} codes {tuple(codes.shape)}")
+    y = out if out is not None else torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    _check(load_library().lga_mxfp6_gemm(_dev(x, "x", torch.bfloat16), _dev(codes, "codes", torch.uint8),
+                                         _dev(scales, "scales", torch.uint8), _opt(bias, "bias", torch.bfloat16),
+                                         _opt(residual, "residual", torch.bfloat16), _dev(y, "y", torch.bfloat16),
+                                         M, N, K, _stream()))
+    return y
+
+
+# ------------------------------------------------------------------------------------------------ mxfp4-a8, fp8-g128-a8
 def mx8_quantize(x: torch.Tensor, out=None):
     """(M, K) bf16 device activations -> (e4m3fn codes uint8 (M, K), e8m0 scale bytes uint8 (M, K / 32)): MXFP8, the
     fp8 KV cache's scale rule on every 32 consecutive columns of a row (include/litgpt_amd.h). ``out``: the pair to

@@ -42,6 +42,10 @@ Modes:
                                               rounded to MXFP8 where the Linear is compute-bound (the GEMM at M >= 2:
                                               prefill, scoring), for the block-scaled fp8 x fp8 MFMA, and stay bf16
                                               on the one-row and multi-row decode GEMVs
+  "mxfp6"                                     weight-only OCP MXFP6 (``Mxfp6Linear``): six-bit e2m3 codes with one e8m0
+                                              power-of-two scale per 32 weights of a row; 6.25 bits per weight, the
+                                              dequantized weight exact in bf16, bf16 activations.
+                                              in_features must be a multiple of 64
 Group sizes must divide in_features; for a TP row-shard whose width is not a multiple of the requested group
 (e.g. Llama-2-7B mlp.proj at TP=8: 1376) the largest of {128, 64, 32} that divides it is used.
 """
@@ -88,6 +92,7 @@ _MODES = {
     "mxfp4": (ops.FMT_MXFP4, 32),  # Mxfp4Linear: e2m1 codes, one e8m0 scale byte per 32 weights
     "mxfp4-a8": (ops.FMT_MXFP4, 32),  # Mxfp4A8Linear: the same weights; M >= 2 rounds the activations to MXFP8
     "fp8-g128-a8": (ops.FMT_FP8, 128),  # Fp8A8Linear: fp8-g128's weights; the GEMM rounds the activations to MXFP8
+    "mxfp6": (ops.FMT_MXFP6, 32),  # Mxfp6Linear: e2m3 codes, 24 bytes and one e8m0 scale byte per 32 weights
 }
 
 
@@ -438,6 +443,67 @@ class Mxfp4Linear(_Kernels, nn.Module):
                 f"e8m0 block={ops.MXFP4_GROUP}")
 
 
+class Mxfp6Linear(_Kernels, nn.Module):
+    """Weight-only MXFP6 Linear (``mxfp6``): ``qweight`` (N, 3 K / 4) uint8, the 32 six-bit e2m3 codes of a block in 24
+    consecutive bytes (code i in bits 6 i .. 6 i + 5, little-endian), + ``scales`` (N, K / 32) uint8 e8m0 on the GPU.
+    Activations stay bf16; the Linear computes what ``Bf16Linear`` computes on the dequantized weight
+    ``e2m3(code) * 2^(scale - 127)`` (exact in bf16).
+
+    One token -> ``lga_mxfp6_gemv`` (RMSNorm / bias / residual fused), several -> the bf16 MFMA GEMM
+    ``lga_mxfp6_gemm`` that expands the code tile in registers; fc_1 || fc_2 of one token ->
+    ``lga_mxfp6_gemv_swiglu``, of several two GEMMs and ``lga_swiglu``. There is no multi-row decode GEMV: batched and
+    speculative decoding refuse the format (``_Kernels.gemv_rows``)."""
+
+    def __init__(self, in_features: int, out_features: int, bias: Optional[torch.Tensor] = None, device=None):
+        super().__init__()
+        if in_features % ops.MXFP6_K_STEP:
+            raise ValueError(f"in_features={in_features} is not a multiple of {ops.MXFP6_K_STEP}; mxfp6 rows are runs "
+                             f"of 48-B pairs of {ops.MXFP6_GROUP}-weight blocks")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("qweight", torch.empty(out_features, in_features // 4 * 3, dtype=torch.uint8,
+                                                    device=device))
+        self.register_buffer("scales", torch.empty(out_features, in_features // ops.MXFP6_GROUP, dtype=torch.uint8,
+                                                   device=device))
+        self.bias = None if bias is None else nn.Parameter(bias.to(torch.bfloat16), requires_grad=False)
+
+    @property
+    def weight(self) -> torch.Tensor:
+        return self.qweight
+
+    @classmethod
+    def from_float(cls, weight: torch.Tensor, bias: Optional[torch.Tensor],
+                   device: Optional[torch.device] = None, *, mode: str = "mxfp6") -> "Mxfp6Linear":
+        N, K = weight.shape
+        if K % ops.MXFP6_K_STEP:  # before anything touches the device
+            raise ValueError(f"in_features={K} is not a multiple of {ops.MXFP6_K_STEP}; mxfp6 rows are runs of 48-B "
+                             f"pairs of {ops.MXFP6_GROUP}-weight blocks")
+        device = device or (weight.device if weight.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        m = cls(K, N, None if bias is None else bias.detach().to(device), device=device)
+        qw, sc = ops.mxfp6_quantize(weight.detach().to(device))
+        m.qweight.copy_(qw)
+        m.scales.copy_(sc)
+        return m
+
+    def gemv_fuses_norm(self, dual: bool = False) -> bool:
+        """lga_mxfp6_gemv(_swiglu) takes the RMSNorm of rows up to K = 12288."""
+        return self.in_features <= ops.MXFP6_NORM_MAX_K
+
+    def gemv(self, x, res, norm_weight, eps):
+        return ops.mxfp6_gemv(x, self.qweight, self.scales, bias=self.bias, residual=res, norm_weight=norm_weight,
+                              eps=eps)
+
+    def gemm(self, x, res):
+        return ops.mxfp6_gemm(x, self.qweight, self.scales, bias=self.bias, residual=res)
+
+    def gemv_swiglu(self, o, x, norm_weight, eps):
+        return ops.mxfp6_gemv_swiglu(x, self.qweight, self.scales, o.qweight, o.scales, norm_weight=norm_weight,
+                                     eps=eps)
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, out_features={self.out_features}, mxfp6 e2m3, "
+                f"e8m0 block={ops.MXFP6_GROUP}")
+
+
 class Mxfp4A8Linear(Mxfp4Linear):
     """``mxfp4-a8``: an ``Mxfp4Linear`` (same quantizer, buffers and bytes: a checkpoint converted under one mode loads
     under the other) whose several-row product runs on the block-scaled fp8 x fp4 MFMA. Activations are rounded to
@@ -552,7 +618,7 @@ def kernels(lin: nn.Module) -> _Kernels:
     raise NotImplementedError(
         "Linear without MI355X weights: move the model to the GPU in bf16, or convert it with "
         "lit_gpt.quantize.QuantizedPrecision('int4-g128' | 'nf4' | 'bnb.int8' | 'fp8-g128' | 'fp8-g128-a8' | 'mxfp4' | "
-        "'mxfp4-a8')"
+        "'mxfp4-a8' | 'mxfp6')"
         ".convert_module(model) (the --quantize "
         "flag)")
 
@@ -607,11 +673,12 @@ class QuantizedPrecision:
     def convert_module(self, module: nn.Module, device: Optional[torch.device] = None) -> nn.Module:
         """Replace every ``nn.Linear`` (lm_head included) by a ``QuantLinear`` (``Int8Linear`` for ``bnb.int8``,
         ``Fp8Linear`` for ``fp8-g128``, ``Fp8A8Linear`` for ``fp8-g128-a8``, ``Mxfp4Linear`` for ``mxfp4``,
-        ``Mxfp4A8Linear`` for ``mxfp4-a8``) quantized on ``device``."""
+        ``Mxfp4A8Linear`` for ``mxfp4-a8``, ``Mxfp6Linear`` for ``mxfp6``) quantized on ``device``."""
         for name, child in list(module.named_children()):
             if isinstance(child, nn.Linear):
                 cls = {"bnb.int8": Int8Linear, "fp8-g128": Fp8Linear, "fp8-g128-a8": Fp8A8Linear,
-                       "mxfp4": Mxfp4Linear, "mxfp4-a8": Mxfp4A8Linear}.get(self.mode, QuantLinear)
+                       "mxfp4": Mxfp4Linear, "mxfp4-a8": Mxfp4A8Linear,
+                       "mxfp6": Mxfp6Linear}.get(self.mode, QuantLinear)
                 setattr(module, name, cls.from_float(child.weight, child.bias, mode=self.mode, device=device))
             else:
                 self.convert_module(child, device)

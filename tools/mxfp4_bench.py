@@ -136,13 +136,12 @@ def gemm(out):
     _write(out, result)
 
 
-def e2e(out, prompt_len=2048, steps=255):
+def e2e(out, prompt_len=2048, steps=255, modes=(None, "fp8-g128", "int4-g128", "mxfp4")):
     from generate.base import build_model, generate
     from lit_gpt import Config
 
     dev = torch.device("cuda")
     cfg = Config.from_name("Llama-2-7b-hf")
-    modes = (None, "fp8-g128", "int4-g128", "mxfp4")
     models = {str(q or "bf16"): build_model(cfg, quantize=q, device=dev, max_seq_length=prompt_len + steps + 1)
               for q in modes}
     g = torch.Generator(device="cpu").manual_seed(1234)
@@ -164,7 +163,7 @@ def e2e(out, prompt_len=2048, steps=255):
         for k, m in models.items():
             pre[k].append(run(m, 1))
             full[k].append(run(m, steps + 1))
-    result = {"what": f"synthetic Llama-2-7B, {prompt_len}-token prompt, {steps} greedy steps, graph replay; four "
+    result = {"what": f"synthetic Llama-2-7B, {prompt_len}-token prompt, {steps} greedy steps, graph replay; the "
                       "models in turn, 3 rounds after a warm-up; decode = whole call - prefill-only call", "modes": {}}
     for k, m in models.items():
         dec = [f - p for f, p in zip(full[k], pre[k])]
